@@ -12,10 +12,21 @@ A "step" is one full optimisation step of the hot path on one synthetic batch pe
 4 prior heads, per-category sampled softmax over 8192 negatives, backward, RCCL gradient exchange, fused AdamW over all
 parameters including the 454k x 256 item table.  Workload = BASELINE.json configs[1] (cfg1: L=200, P=8, D=256,
 8 layers x 8 heads, C=4 prior heads, N=453 938 items, B=128 per GPU, bf16-mixed).  Inputs are generated on the device
-before the timed region.  The timed region is pure wall clock (no events inside it); per-kernel HIP events are collected
-in a SEPARATE pass afterwards.  Rank 0 prints ONE JSON line.
+before the timed region.  The timed region is pure wall clock (no events inside it).  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, primes the step graphs, runs W warm-up and K timed steps and prints the line (`ms_per_step` = the
+timed region / K).  `--dump-outputs DIR` then also writes what the last timed step computed as float32 / float64 `.npy`
+files (at most 64 MB): train mode what the step returns to its caller (`loss.npy`, the per-head losses and logs), eval mode
+the fused per-head top-k (`topk_values.npy`, `topk_indices.npy`).  The batches and the initial model are seeded: the same
+arguments give the same inputs run to run, and the outputs agree to rounding.  Not bit for bit: by default the loss backward
+accumulates in float atomics whose order varies, and the parameters the last step starts from carry every earlier step's
+last bits.  The parameters themselves are not written: Adam turns those bits of near-zero gradient entries into updates of up
+to the learning rate, so after W + K steps they differ by far more than rounding.  MHR_DETERMINISTIC=1 selects the
+order-independent reductions: two such runs give bitwise equal outputs, at about 0.8 ms more per cfg1 step.
+
+`--full` adds the measurements that take runs of their own: the idle-queue host probe, per-kernel HIP events collected in a
+SEPARATE evented pass after the timed region, the eval leg, the GPU clocks, the CPU baseline and `--emulate-world`.  Extra
+objects on a `--full` line:
   roofline     - the dominant kernel of the train step (by summed HIP-event time of the evented pass), priced by its
                  ALGORITHMIC bytes against 8 TB/s when its arithmetic intensity is below the machine balance
                  (2.5 PFLOP/s / 8 TB/s = 312 flop/B), else by its ALGORITHMIC flops against the dense bf16 MFMA peak;
@@ -50,6 +61,11 @@ def parse(argv=None):
     ap.add_argument("--config", default="cfg1")
     ap.add_argument("--mode", default="train", choices=["train", "eval"])
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch override (0 = config)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline figure: host probe, evented pass, eval leg, GPU clocks, CPU "
+                         "baseline, --emulate-world (the --no-* options below switch single ones off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-eval-leg", action="store_true", help="train mode: skip the eval sub-object")
     ap.add_argument("--no-host-probe", action="store_true", help="skip the 5 untimed steps that measure the host's issue time")
@@ -60,8 +76,9 @@ def parse(argv=None):
     ap.add_argument("--event-steps", type=int, default=10, help="steps of the evented pass (outside the timed region)")
     ap.add_argument("--pretrain-steps", type=int, default=0, help="eval mode: take this many train steps first (diagnostic)")
     ap.add_argument("--emulate-world", type=int, default=0,
-                    help="one GPU: time the table-side kernels of the optimizer step (id sort, row buffer, segment sum + fix-up, lazy row "
-                         "AdamW) on W ranks' worth of exchanged ids / rows - the part of a data-parallel step that does not shrink with W")
+                    help="with --full, one GPU: time the table-side kernels of the optimizer step (id sort, row buffer, segment sum + "
+                         "fix-up, lazy row AdamW) on W ranks' worth of exchanged ids / rows - the part of a data-parallel step that does "
+                         "not shrink with W")
     return ap.parse_args(argv)
 
 
@@ -375,6 +392,46 @@ def _gpu_clocks():
 
 
 # ------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed
+# ------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def _dump_name(name):
+    return "".join(c if (c.isalnum() or c in "._-") else "_" for c in name)
+
+
+def _host_array(v):
+    """A device tensor or a number -> numpy float64 (float32 tensors stay float32)."""
+    import numpy as np
+    import torch
+    if torch.is_tensor(v):
+        v = v.detach()
+        return v.float().cpu().numpy() if v.dtype in (torch.float32, torch.bfloat16, torch.float16) else v.double().cpu().numpy()
+    return np.asarray(v, dtype=np.float64)
+
+
+def snapshot_train(last):
+    """-> {name: numpy array}: what the step returns to its caller (the loss, the per-head losses and logs).  The parameters
+    are not part of it: after many Adam steps they carry the run's own rounding history (see the module docstring)."""
+    import numbers
+    import torch
+    return {_dump_name(k): _host_array(v) for k, v in last.items() if torch.is_tensor(v) or isinstance(v, numbers.Number)}
+
+
+def snapshot_eval(fused):
+    return {"topk_values": _host_array(fused.values), "topk_indices": _host_array(fused.indices)}
+
+
+def write_dump(arrays, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+# ------------------------------------------------------------------------------------------------
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -382,6 +439,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
+    if args.emulate_world and not args.full:
+        raise SystemExit("bench.py: --emulate-world is a measurement of --full")
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     import torch
@@ -460,9 +519,10 @@ def main():
                "mhr_hstu_attn_fwd", "mhr_hstu_attn_bwd", "mhr_adam_rows", "mhr_adam_rows_lazy", "mhr_embedding_gather_fwd",
                "mhr_sparse_rows_segment_sum", "mhr_topk_select", "mhr_topk_select_sliced", "mhr_sum_rows_into", "mhr_embedding_gather_step"]
 
-    def run_leg(mode, warmup, steps, event_steps):
-        """-> dict(elapsed, host_enqueue, host_alone, prof, prof_max, last, batches, B).  Wall-clock pass first (nothing but
-        the steps between the two syncs), then - outside it - the evented pass and the idle-queue host probe."""
+    def run_leg(mode, warmup, steps, event_steps, host_probe=False, snapshot=None):
+        """-> dict(elapsed, host_enqueue, host_alone, prof, prof_max, last, batches, B, outputs).  Wall-clock pass first (nothing
+        but the steps between the two syncs), then - outside it - `snapshot(last)` of the last timed step's results, the
+        idle-queue host probe and the evented pass (event_steps > 0)."""
         B = cfg["train_batch_size"] if mode == "train" else cfg["eval_batch_size"]
         n_steps = warmup + steps
         if mode == "train":
@@ -485,7 +545,7 @@ def main():
             def step(i, eager=False):
                 fused, pu, pi, tt, _ = trainer._full_sort_batch_eval(batches[i % len(batches)], graph=False if eager else None)
                 trainer.eval_collector.eval_batch_collect(fused, pu, pi)
-                return None
+                return fused
         ops.PROFILE = None
         if mode == "train" and not args.no_graph:
             # one captured step graph per batch signature (shapes + the packed encoder's row capacity): every signature gets its
@@ -510,8 +570,9 @@ def main():
         host_enqueue = time.perf_counter() - t0          # the host is done issuing; the GPU may still be working
         sync()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        outputs = snapshot(last) if (snapshot is not None and last is not None) else None   # before later steps overwrite it
         host_alone = []                                   # host cost of issuing ONE step into an idle queue
-        for i in range(0 if args.no_host_probe else 5):
+        for i in range(5 if host_probe else 0):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             step(n_steps + i)
@@ -519,7 +580,7 @@ def main():
         sync()
         host_alone = sorted(host_alone)[len(host_alone) // 2] if host_alone else float('nan')
         prof, prof_max = {}, {}
-        if event_steps > 0 and not args.no_kernel_events:
+        if event_steps > 0:
             # evented pass: every C-ABI call of EVENTED bracketed by HIP events on its launch stream.  Host-issued launches
             # (a replayed hipGraph has no per-kernel events), a few steps, outside the timed region.
             ops.PROFILE = {k: [] for k in EVENTED}
@@ -533,7 +594,7 @@ def main():
             prof = ops.profile_summary()
             ops.PROFILE = None
         return dict(elapsed=elapsed, host_enqueue=host_enqueue, host_alone=host_alone, prof=prof, prof_max=prof_max,
-                    last=last, batches=batches, B=B, steps=steps, event_steps=max(1, event_steps))
+                    last=last, batches=batches, B=B, steps=steps, event_steps=max(1, event_steps), outputs=outputs)
 
     def catalog_roofline(leg, Bev):
         """The launch that scores the whole catalog (the two threshold-sample launches of a step score 1/14 + 1/222 of it and
@@ -672,11 +733,17 @@ def main():
         for i in range(args.pretrain_steps):
             trainer.train_step_fn(pb[i % 4])
         torch.cuda.synchronize()
-    main_leg = legs[args.mode] = run_leg(args.mode, args.warmup, args.steps, args.event_steps)
+    # a plain run: the timed steps and nothing else; --full: the host probe and the evented pass behind them, then the eval leg
+    host_probe = args.full and not args.no_host_probe
+    event_steps = args.event_steps if (args.full and not args.no_kernel_events) else 0
+    snapshot = None
+    if args.dump_outputs and rank == 0:
+        snapshot = snapshot_train if args.mode == "train" else snapshot_eval
+    main_leg = legs[args.mode] = run_leg(args.mode, args.warmup, args.steps, event_steps, host_probe=host_probe, snapshot=snapshot)
     graph_expected = bool(args.mode == "train" and not args.no_graph and (trainer._graph_ok(main_leg["batches"][0]) or getattr(trainer, "_graph_failed", False)))
     graph_on = bool(getattr(trainer, "graph_active", False))
-    if args.mode == "train" and not args.no_eval_leg:
-        legs["eval"] = run_leg("eval", 3, 10, min(args.event_steps, 5))
+    if args.full and args.mode == "train" and not args.no_eval_leg:
+        legs["eval"] = run_leg("eval", 3, 10, min(event_steps, 5), host_probe=host_probe)
 
     if rank == 0:
         B = main_leg["B"]
@@ -783,16 +850,18 @@ def main():
             eo["host_enqueue_ms_per_step"] = round(1000 * ev["host_enqueue"] / ev["steps"], 3)
             eo["graph_active"] = any(g_.graph is not None for g_ in trainer.__dict__.get("_eval_graphs", {}).values())
             out["eval"] = eo
-        if args.emulate_world > 1 and world == 1 and args.mode == "train" and getattr(trainer.optimizer, "lazy", False):
+        if args.full and args.emulate_world > 1 and world == 1 and args.mode == "train" and getattr(trainer.optimizer, "lazy", False):
             out["emulated_world"] = emulate_world(args.emulate_world)
-        clk = _gpu_clocks()
+        clk = _gpu_clocks() if args.full else None
         if clk:
             out["gpu_clocks_after_run"] = clk
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(dict(spec["cfg"]), N)
             except Exception as e:  # noqa: BLE001 - the baseline must not kill the bench line
                 out["cpu_baseline"] = {"value": None, "error": repr(e)[:200]}
+        if args.dump_outputs:
+            write_dump(main_leg["outputs"] or {}, args.dump_outputs)
         print(json.dumps(out), flush=True)
         if out.get("graph_expected") and not out["graph_active"] and world == 1:
             rc_fail = "bench.py: the train step was expected to replay from a hipGraph and did not"

@@ -372,3 +372,32 @@ def test_bench_launches_its_own_ranks_and_checks_the_world_size(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "WORLD_SIZE=2" in str(e.value.code) and "--gpus 4" in str(e.value.code)
+
+
+def test_bench_extras_are_behind_full_and_dumps_stay_in_budget(monkeypatch, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline only: every other measurement needs `--full`
+    (`--emulate-world` without it is refused before anything touches the GPU).  `--dump-outputs` writes what the step returns
+    to its caller - losses and logs, not the parameters - as float32 / float64 .npy files within 64 MB, the same arrays on
+    every call."""
+    import importlib
+    import sys as _sys
+    bench = importlib.import_module("bench")
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(_sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--emulate-world", "8"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert "--full" in str(e.value.code)
+
+    last = {"loss": torch.tensor(1.25), "head_nce_a/b_loss": torch.tensor(0.5), "n": 3, "acc": torch.tensor([1, 2]), "note": "x"}
+    s1, s2 = bench.snapshot_train(last), bench.snapshot_train(last)
+    assert set(s1) == {"loss", "head_nce_a_b_loss", "n", "acc"}
+    for k, v in s1.items():
+        assert v.dtype in (np.float32, np.float64) and np.array_equal(v, s2[k])
+    bench.write_dump(s1, str(tmp_path / "out"))
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(k + ".npy" for k in s1)
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")) <= 64 << 20
+    assert float(np.load(tmp_path / "out" / "loss.npy")) == 1.25

@@ -1,9 +1,9 @@
-"""Condense rocprofv3 output (gpurun_out/…) into the small, tracked summaries under profiles/.
+"""Condense rocprofv3 output (profile_out/…, written by tools/profile_round.sh) into the small, tracked summaries under profiles/.
 
     python tools/summarize_profiles.py r01
 
-reads   gpurun_out/prof_<round>_{train,eval}/*/*_kernel_stats.csv      (rocprofv3 --kernel-trace --stats)
-        gpurun_out/pmc_<round>_{fetch,write}/*/*_counter_collection.csv (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)
+reads   profile_out/prof_<round>_{train,eval}/*/*_kernel_stats.csv      (rocprofv3 --kernel-trace --stats)
+        profile_out/pmc_<round>_{fetch,write}/*/*_counter_collection.csv (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)
 writes  profiles/<round>_{train,eval}_kernel_stats.csv   top kernels, names shortened
         profiles/<round>_hbm_traffic.json                 per-kernel HBM bytes per launch, corrected as
                                                           MI355X_MICROARCH.md prescribes (FETCH_SIZE is in KB and
@@ -17,6 +17,7 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RAW = os.path.join(ROOT, "profile_out")            # raw bench lines and rocprofv3 output of tools/profile_round.sh
 csv.field_size_limit(1 << 30)
 
 
@@ -37,7 +38,7 @@ def newest(pattern):
 
 
 def kernel_stats(rnd, leg, top=40):
-    f = newest(os.path.join(ROOT, "gpurun_out", f"prof_{rnd}_{leg}", "*", "*_kernel_stats.csv"))
+    f = newest(os.path.join(RAW, f"prof_{rnd}_{leg}", "*", "*_kernel_stats.csv"))
     if f is None:
         return
     rows = list(csv.DictReader(open(f)))
@@ -58,7 +59,7 @@ def kernel_stats(rnd, leg, top=40):
 def traffic(rnd, mode=""):
     acc = {}
     for leg, counter, scale in (("fetch", "FETCH_SIZE", 2.0 * 1024), ("write", "WRITE_SIZE", 1024.0)):
-        f = newest(os.path.join(ROOT, "gpurun_out", f"pmc_{rnd}_{mode}{leg}", "*", "*_counter_collection.csv"))
+        f = newest(os.path.join(RAW, f"pmc_{rnd}_{mode}{leg}", "*", "*_counter_collection.csv"))
         if f is None:
             continue
         for r in csv.DictReader(open(f)):
@@ -90,7 +91,7 @@ def mfma_util(rnd, mode=""):
     (SURVEY 8d).  SQ_VALU_MFMA_BUSY_CYCLES counts matrix-pipe cycles summed over the chip's 1024 SIMDs (32 per
     v_mfma_f32_32x32x16_bf16, MI355X_MICROARCH.md); GRBM_GUI_ACTIVE is summed over the 8 XCDs, so GRBM / 8 is the launch's
     length in shader cycles:  util = MFMA_BUSY / (1024 x GRBM / 8)."""
-    f = newest(os.path.join(ROOT, "gpurun_out", f"pmc_{rnd}_{mode}mfma", "*", "*_counter_collection.csv"))
+    f = newest(os.path.join(RAW, f"pmc_{rnd}_{mode}mfma", "*", "*_counter_collection.csv"))
     if f is None:
         return
     per = {}
@@ -129,7 +130,7 @@ def full_launches(rnd):
     for leg, names, per_step in (("eval", ("catalog_emit_sliced_kernel", "catalog_emit_wide_kernel"), 3),
                                  ("train", ("nce_fwd_d_kernel", "nce_bwd_n_kernel", "gather_step_kernel", "hstu_attn_bwd_kernel",
                                             "hstu_attn_fwd_kernel"), None)):
-        f = newest(os.path.join(ROOT, "gpurun_out", f"prof_{rnd}_{leg}", "*", "*_kernel_trace.csv"))
+        f = newest(os.path.join(RAW, f"prof_{rnd}_{leg}", "*", "*_kernel_trace.csv"))
         if f is None:
             continue
         durs = {}
@@ -151,7 +152,7 @@ def full_launches(rnd):
 
 
 def readme(rnd):
-    """profiles/README.md from the condensed files + the bench lines (gpurun_out/bench_<rnd>_{train,eval}.json)."""
+    """profiles/README.md from the condensed files + the bench lines (profile_out/bench_<rnd>_{train,eval}.json)."""
     P = os.path.join(ROOT, "profiles")
 
     def table(f, n, steps):
@@ -160,7 +161,7 @@ def readme(rnd):
                          for r in rows[:n] if r[3])
 
     for src, dst in ((f"bench_{rnd}_train.json", f"{rnd}_bench_train.json"), (f"bench_{rnd}_eval.json", f"{rnd}_bench_eval.json")):
-        f = os.path.join(ROOT, "gpurun_out", src)
+        f = os.path.join(RAW, src)
         if os.path.exists(f):
             json.dump(json.load(open(f)), open(os.path.join(P, dst), "w"), indent=1)
     bt = json.load(open(os.path.join(P, f"{rnd}_bench_train.json")))
@@ -179,13 +180,13 @@ def readme(rnd):
     steps = 25
     md = f"""# profiles/ - round {rnd[1:]} (one MI355X, gfx950, ROCm 7.2, cfg1 = HSTU Pixel8M shape)
 
-All files here are condensed by `tools/summarize_profiles.py {rnd}` from rocprofv3 output written under `gpurun_out/` on the GPU box
+All files here are condensed by `tools/summarize_profiles.py {rnd}` from rocprofv3 output written under `profile_out/`
 by `tools/profile_round.sh {rnd}` (round 1's files, `r01_*`, are kept next to them for comparison).
 
 | File | Command it comes from |
 |---|---|
-| `{rnd}_bench_train.json` | `python bench.py --steps 50 --warmup 10` - the bench line itself (train step replayed from a hipGraph; eval / gather / cpu_baseline sub-objects) |
-| `{rnd}_bench_eval.json` | `python bench.py --mode eval --steps 20 --warmup 5` |
+| `{rnd}_bench_train.json` | `python bench.py --full --steps 50 --warmup 10` - the bench line itself (train step replayed from a hipGraph; eval / gather / cpu_baseline sub-objects) |
+| `{rnd}_bench_eval.json` | `python bench.py --full --mode eval --steps 20 --warmup 5` |
 | `{rnd}_train_kernel_stats.csv` | `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-cpu-baseline --no-host-probe --no-eval-leg --no-kernel-events --steps 20 --warmup 5` ({steps} steps traced) |
 | `{rnd}_eval_kernel_stats.csv` | the same with `--mode eval` |
 | `{rnd}_hbm_traffic.json`, `{rnd}_hbm_traffic_eval.json` | `rocprofv3 --pmc FETCH_SIZE -- python bench.py ... --steps 4 --warmup 4` and the same with `--pmc WRITE_SIZE` (separate passes); FETCH_SIZE KB x 2 (gfx950 correction), WRITE_SIZE KB x 1 |
@@ -241,7 +242,7 @@ if __name__ == "__main__":
     mfma_util(rnd, "eval_")
     full_launches(rnd)
     for extra in ("emu", "dp2_gloo", "dp1_rccl"):                       # bench --emulate-world / the two-rank gloo rehearsal lines, if the set made them
-        f = os.path.join(ROOT, "gpurun_out", f"bench_{rnd}_{extra}.json")
+        f = os.path.join(RAW, f"bench_{rnd}_{extra}.json")
         if os.path.exists(f) and os.path.getsize(f):
             json.dump(json.loads(open(f).read().strip().splitlines()[-1]), open(os.path.join(ROOT, "profiles", f"{rnd}_bench_{extra}.json"), "w"), indent=1)
     readme(rnd)
