@@ -465,6 +465,15 @@ int mhr_nce_bwd_negs(const void* qn, const void* negs, const uint32_t* supp, int
  *   fix_any [n_groups, round_up(n_p_rows, 256)] int32 (caller zeroes): != 0 where a target row has any suppressed negative;
  *   bit k = a suppressed negative in the 32-negative tiles [k << s, (k + 1) << s), s the smallest shift with ceil(n_tiles / 2^s) <= 32
  *   (the token kernels read only the flagged groups of the row's column of the bit table).
+ * mhr_nce_fix_bits_filtered: the same table for dim 128 / 256 without the full product for pairs a 64-column prefix already
+ *   decides: a norm pass over the negatives, a prefix pass that rejects a pair only where prefix product + |target remainder|
+ *   |negative remainder| + rounding slack <= thres (Cauchy-Schwarz; no assumption on norms or thres; NaN operands are never
+ *   rejected) and lists the (32-row fragment, tile) units with a surviving pair, and an exact pass over that list with the
+ *   instruction sequence of mhr_nce_fix_bits.  Contract shared by both entry points: fix_any, fix_slot_of_row and every word of
+ *   a tile group FLAGGED in fix_any[row] are defined (and identical, bit for bit, between the two); words of unflagged groups
+ *   are unspecified - every reader tests fix_any first.  workspace: mhr_nce_fix_bits_filtered_workspace_bytes(n_p_rows, n_neg,
+ *   n_groups) bytes, 16-byte aligned, contents need no initialisation; after the call its first int32 holds the number of
+ *   listed units (for tools; nothing on the product path reads it on the host).
  * The normalised targets are a property of the TARGET ROW: pn_rows [n_p_rows, dim] bf16 = bf16(p_rows / |p_rows|) and p_inv
  *   [n_p_rows] f32 (mhr_l2norm_rows, once per step) are shared by all tokens and groups; `pn` / `p_inv` below are these tables.
  * mhr_nce_shared_fwd_tokens: per token: s_pos = qn_row . pn_rows[p_idx],
@@ -481,6 +490,11 @@ int mhr_nce_bwd_negs(const void* qn, const void* negs, const uint32_t* supp, int
 int mhr_nce_fix_bits(const void* p_rows, int io_dtype, int64_t n_p_rows, const void* negs, int n_neg, int dim,
                      int n_groups, float thres, uint32_t* fix_words, const int32_t* fix_row_list,
                      const int32_t* fix_n_rows, int32_t* fix_slot_of_row, int32_t* fix_any, void* stream);
+int64_t mhr_nce_fix_bits_filtered_workspace_bytes(int64_t n_p_rows, int n_neg, int n_groups);
+int mhr_nce_fix_bits_filtered(const void* p_rows, int io_dtype, int64_t n_p_rows, const void* negs, int n_neg, int dim,
+                              int n_groups, float thres, uint32_t* fix_words, const int32_t* fix_row_list,
+                              const int32_t* fix_n_rows, int32_t* fix_slot_of_row, int32_t* fix_any,
+                              void* workspace, int64_t workspace_bytes, void* stream);
 int mhr_nce_shared_fwd_tokens(const void* pn_rows, int64_t n_p_rows, const int32_t* p_idx,
                               const int32_t* tok2row, int n_groups, const int32_t* n_tok_dev, int tok_cap,
                               int row_cap, const void* qn_row, const float* sum_row, const int32_t* n_valid_row,

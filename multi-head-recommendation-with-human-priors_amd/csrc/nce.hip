@@ -607,6 +607,261 @@ __global__ __launch_bounds__(256, 2) void nce_fix_bits_kernel(const IT* __restri
 }
 
 // ------------------------------------------------------------------------------------------
+// the same table through a prefix filter (mhr_nce_fix_bits_filtered): three launches
+// ------------------------------------------------------------------------------------------
+// Almost every bit of the table is zero, and provably so from the first Kp = FIX_KPS * 16 columns.  With t the bf16
+// target row as load_norm_frags makes it, n a row of negs, p / r the prefix / remaining columns:
+//     s = t.n = s_p + s_r,   |s_r| <= |t_r| |n_r|   (Cauchy-Schwarz)
+// so  s_p + |t_r| |n_r| <= thres  proves the bit zero.  What the kernels compare are fp32 values, so with u = 2^-24:
+//   * the exhaustive kernel's accumulator S satisfies |S - s| <= D * 2u * sum_k |t_k n_k| <= 2 D u |t| |n|  (bf16 products
+//     are exact in fp32; D additions, each within 2u of its partial sum even if the matrix pipe truncates), and the
+//     prefix accumulator S_p likewise |S_p - s_p| <= 2 Kp u |t| |n|;
+//   * the norms are fp32 sums of D non-negative squares and one square root: relative error <= (D + 2) u each, so the
+//     product of two computed norms is within (2 D + 8) u |t| |n| of |t_r| |n_r|;
+//   * squares and products below 2^-126 may be flushed: D * 2^-126 is added to every sum of squares before the root
+//     (the computed norm can only be too large then) and 2^-100 is taken off the threshold;
+//   * the limit itself is three fp32 operations on terms bounded by |thres| + 2 |t| |n|: |thres| 2^-20 is taken off too.
+// (2 D + 2 Kp + 2 D + 8 + 6) u < 4 D * 2u = D * 2^-21 for D >= 128, Kp = 64: FIX_EPS below.  None of it is tuned: the
+// test is "reject only if S_p <= lim", so NaN operands (a zero target row: inv = inf, fragments NaN) and infinities
+// do not reject, and phase B evaluates such pairs exactly like the exhaustive kernel.  Nothing assumes unit norms or a
+// particular thres; a filter that cannot reject only costs time.  lim uses the TILE maximum of the negatives' norms
+// (the negatives sit on the accumulator registers, one scalar per tile keeps the epilogue at one compare per element).
+#ifndef MHR_FIX_KPS
+#define MHR_FIX_KPS 4                                        // (tools/variant.py build "MHR_FIX_KPS=2": the prefix-width experiment)
+#endif
+constexpr int FIX_KPS = MHR_FIX_KPS;                         // prefix k-steps: Kp = 64 columns (why not 32 / 128)
+constexpr int FIX_SUB = FIX_KPS <= 4 ? 4 : 2;                // tiles per ring step of the prefix pass (16 KiB of images)
+static_assert(FIX_KPS == 2 || FIX_KPS == 4 || FIX_KPS == 8, "the prefix image is a Tile<FIX_KPS> of whole 1-KiB pieces");
+template <int NKS>
+constexpr float FIX_EPS = (float)(NKS * 16) * 0x1p-21f;
+template <int NKS>
+constexpr float FIX_SS_FLOOR = (float)(NKS * 16) * 0x1p-126f;
+
+__device__ __forceinline__ float nan_max(float m, float x) { return (x > m || x != x) ? x : m; }   // NaN wins: it must not reject
+
+// Norm pass: per (group, 32-negative tile) the largest remainder norm and the largest full norm of its rows (padding rows
+// of the last tile included: the exhaustive kernel tests them too); also zeroes the candidate counter.  One wave per
+// tile: lane (c, h) reads chunk c of rows 2 i + h, so every load instruction covers two whole rows.
+template <int NKS>
+__global__ __launch_bounds__(256) void nce_neg_tile_norms_kernel(const bf16_t* __restrict__ negs, int n_neg,
+                                                                 float* __restrict__ b_rem, float* __restrict__ b_full,
+                                                                 int32_t* __restrict__ counter) {
+  using T = sg::Tile<NKS>;
+  constexpr int CH = T::CH, RPI = 64 / CH;                   // 16-byte chunks per row; rows per load instruction
+  static_assert(CH == 16 || CH == 32, "a row is a whole number of lanes of one wave");
+  const int n_tiles = (n_neg + 31) >> 5;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *counter = 0;
+  const int lane = threadIdx.x & 63, c = lane % CH, h = lane / CH;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= n_tiles) return;
+  const bf16_t* src = negs + ((int64_t)blockIdx.y * n_tiles + t) * (32 * T::DIM) + h * T::DIM + c * 8;
+  float m_rem = 0.f, m_full = 0.f;
+#pragma unroll 4
+  for (int i = 0; i < 32 / RPI; ++i) {
+    float v[8];
+    load8<bf16_t>(src + i * RPI * T::DIM, v);
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ss += v[j] * v[j];
+    float sr = c >= 2 * FIX_KPS ? ss : 0.f;
+#pragma unroll
+    for (int d = CH / 2; d >= 1; d >>= 1) {
+      ss += __shfl_xor(ss, d, 64);
+      sr += __shfl_xor(sr, d, 64);
+    }
+    m_rem = nan_max(m_rem, sqrtf(sr + FIX_SS_FLOOR<NKS>));
+    m_full = nan_max(m_full, sqrtf(ss + FIX_SS_FLOOR<NKS>));
+  }
+#pragma unroll
+  for (int d = 32; d >= CH; d >>= 1) {
+    m_rem = nan_max(m_rem, __shfl_xor(m_rem, d, 64));
+    m_full = nan_max(m_full, __shfl_xor(m_full, d, 64));
+  }
+  if (lane == 0) {
+    b_rem[(int64_t)blockIdx.y * n_tiles + t] = m_rem;
+    b_full[(int64_t)blockIdx.y * n_tiles + t] = m_full;
+  }
+}
+
+// Phase A: nce_fix_bits_kernel's skeleton (same grid, same row fragments, same ring) over the first Kp columns only:
+// FIX_KPS MFMAs per fragment and tile, 128 bytes of every negative row through the ring (a Tile<FIX_KPS> image whose
+// source rows are DIM apart).  Writes a zero word for every (row, tile) and appends each (row fragment, tile) with a pair
+// it cannot reject to the candidate list (sized for all of them: no overflow case); phase B overwrites those words.
+template <int NKS, typename IT>
+__global__ __launch_bounds__(256, 4) void nce_fix_prefix_kernel(const IT* __restrict__ p_rows, int n_rows, const bf16_t* negs,
+                                                                int n_neg, float thres, uint32_t* __restrict__ fixw,
+                                                                int n_rows_pad, int tiles_per_slice,
+                                                                const int32_t* __restrict__ row_list, const int32_t* __restrict__ n_list,
+                                                                int32_t* __restrict__ slot_of_row,
+                                                                const float* __restrict__ b_rem, const float* __restrict__ b_full,
+                                                                int32_t* __restrict__ counter, int32_t* __restrict__ cand) {
+  using T = sg::Tile<NKS>;
+  using TP = sg::Tile<FIX_KPS>;
+  constexpr int RF = 2;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int n_tiles = (n_neg + 31) >> 5;
+  negs += (int64_t)blockIdx.z * ((n_neg + 31) & ~31) * T::DIM;
+  fixw += (int64_t)blockIdx.z * n_tiles * n_rows_pad;
+  b_rem += (int64_t)blockIdx.z * n_tiles;
+  b_full += (int64_t)blockIdx.z * n_tiles;
+  const int t0 = blockIdx.y * tiles_per_slice, t1 = min(n_tiles, t0 + tiles_per_slice);
+  if (t0 >= t1) return;
+  const int n_live = row_list ? min(n_list[blockIdx.z], n_rows_pad) : n_rows;
+  if ((int)blockIdx.x * 256 >= n_live) return;
+  if (row_list) {
+    row_list += (int64_t)blockIdx.z * n_rows_pad;
+    slot_of_row += (int64_t)blockIdx.z * n_rows;
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, half = lane >> 5;
+  bf16x8 frag[RF][FIX_KPS];
+  int row[RF];
+  float a_rem[RF], a_eps[RF];            // |t_r| and FIX_EPS |t| of my row (lanes = target rows)
+#pragma unroll
+  for (int f = 0; f < RF; ++f) {
+    row[f] = blockIdx.x * 256 + wave * 64 + f * 32 + r;
+    const bool live = row[f] < n_live;
+    int src_row = row[f];
+    if (row_list) {
+      src_row = live ? row_list[row[f]] : 0;
+      if (live && half == 0 && blockIdx.y == 0) slot_of_row[src_row] = row[f];
+    }
+    const IT* src = p_rows + (live ? (int64_t)src_row * T::DIM : 0);
+    const float inv = row_inv_norm<NKS, IT>(src, live, half);
+    bf16x8 full[NKS];
+    load_norm_frags<NKS, IT>(src, live, half, inv, full);
+    float sp = 0.f, sr = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = (float)full[ks][j];
+        if (ks < FIX_KPS) sp += v * v;
+        else sr += v * v;
+      }
+    }
+    sp += __shfl_xor(sp, 32, 64);
+    sr += __shfl_xor(sr, 32, 64);
+    a_rem[f] = sqrtf(sr + FIX_SS_FLOOR<NKS>);
+    a_eps[f] = FIX_EPS<NKS> * sqrtf(sp + sr + FIX_SS_FLOOR<NKS>);
+#pragma unroll
+    for (int ks = 0; ks < FIX_KPS; ++ks) frag[f][ks] = full[ks];
+  }
+  const float thr_lo = thres - fabsf(thres) * 0x1p-20f - 0x1p-100f;
+  const int32_t frag0 = ((int32_t)blockIdx.z * (n_rows_pad >> 5) + blockIdx.x * 8 + wave * RF) * n_tiles;   // + f * n_tiles + t
+  using P = sg::DmaPieces<FIX_KPS>;
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  P dp;
+  dp.init(wv, lane, T::ROW_BYTES);
+  // A ring step is FIX_SUB consecutive tiles (their prefix images side by side in one slot): the same bytes in flight
+  // and the same MFMA count between two barriers as the exhaustive kernel's 256-column tile.  One 4-KiB tile per
+  // step leaves ~300 cycles between barriers and a two-step lookahead shorter than the memory latency.
+  constexpr int SLOT = FIX_SUB * TP::BYTES;
+  const int t_last = t1 - 1;
+  auto dma_step = [&](auto slot_c, int tn) {       // tiles tn .. tn + FIX_SUB - 1 (clamped: redundant copies keep vmcnt uniform)
+    auto f = [&](auto j_c) {
+      constexpr int j = decltype(j_c)::value / P::PW, k = decltype(j_c)::value % P::PW;
+      dp.template piece<k>(smem + decltype(slot_c)::value * SLOT + j * TP::BYTES,
+                           reinterpret_cast<const char*>(negs) + (int64_t)min(tn + j, t_last) * (32 * T::ROW_BYTES));
+    };
+    sg::static_for<FIX_SUB * P::PW>(f);
+  };
+  sg::LaneAddr<FIX_KPS> la;
+  la.init(lane);
+  sg::RowAddr<FIX_KPS> ra;
+  ra.init(la, smem);
+  const int n_steps = (t1 - t0 + FIX_SUB - 1) / FIX_SUB;
+  dma_step(std::integral_constant<int, 0>{}, t0);
+  dma_step(std::integral_constant<int, 1>{}, t0 + FIX_SUB);
+  // The tile maxima of the negatives' norms reach the loop as lane values (lane j: tile t0 + FIX_SUB c0 + j) read back
+  // with v_readlane: an ordinary load inside the ring loop would make hipcc wait vmcnt(0) - drain the ring - on every
+  // step.  Here it drains once per CHUNK steps (a multiple of the ring depth, so the slot of a step stays step % 3).
+  constexpr int CHUNK = 60 / FIX_SUB / 3 * 3;
+  static_assert(CHUNK >= 3 && CHUNK * FIX_SUB <= 64, "a chunk's tiles are the lanes of one wave");
+  for (int c0 = 0; c0 < n_steps; c0 += CHUNK) {
+    const int tb = min(t0 + c0 * FIX_SUB + lane, t_last);
+    float bv_rem = b_rem[tb], bv_full = b_full[tb];
+    asm volatile("" : "+v"(bv_rem), "+v"(bv_full));      // the wait for the two loads lands here, not in the loop
+    sg::ring_loop<3>(min(CHUNK, n_steps - c0), [&](auto slot_c, int ic) {
+      constexpr int cur = decltype(slot_c)::value, nxt = (cur + 2) % 3;
+      const int ts = t0 + (c0 + ic) * FIX_SUB;
+      sg::wait_vmcnt<FIX_SUB * P::PW>();
+      sg::ring_barrier();
+      dma_step(std::integral_constant<int, nxt>{}, ts + 2 * FIX_SUB);
+      auto sub = [&](auto j_c) {
+        constexpr int j = decltype(j_c)::value;
+        const int t = ts + j;
+        if (t < t1) {                    // (wave-uniform: only the slice's last step can be short)
+          const float br = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bv_rem), ic * FIX_SUB + j));
+          const float bf = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bv_full), ic * FIX_SUB + j));
+          f32x16 acc[RF];
+#pragma unroll
+          for (int f = 0; f < RF; ++f) acc[f] = sg::zero16();
+          sg::mma_tile_asm<FIX_KPS, RF, cur * SLOT + j * TP::BYTES>(ra, frag, acc);
+#pragma unroll
+          for (int f = 0; f < RF; ++f) {
+            const float lim = thr_lo - a_rem[f] * br - a_eps[f] * bf;
+            bool keep = false;           // some pair of this (fragment, tile) is not provably <= thres
+#pragma unroll
+            for (int g = 0; g < 16; ++g) keep |= !(acc[f][g] <= lim);
+            if (half == 0) fixw[(int64_t)t * n_rows_pad + row[f]] = 0u;
+            if (__any(keep)) {
+              if (lane == 0) cand[atomicAdd(counter, 1)] = frag0 + f * n_tiles + t;
+            }
+          }
+        }
+      };
+      sg::static_for<FIX_SUB>(sub);
+    });
+  }
+  sg::wait_vmcnt<0>();
+}
+
+// Phase B: the candidates exactly.  One wave per candidate (grid-stride, count read from device memory): the fragment's
+// 32 rows through the same helpers, the tile's 32 negatives straight from global memory in the lane layout the ring
+// delivers them in (lane (r, half), k-step ks: columns 16 ks + 8 half .. + 7 of row r), the MFMA sequence of
+// sg::mma_tile_asm (k ascending into one zeroed accumulator), the exhaustive kernel's compare, packing and atomicOr:
+// the accumulators, and so the words, are the exhaustive kernel's.
+template <int NKS, typename IT>
+__global__ __launch_bounds__(256) void nce_fix_exact_kernel(const IT* __restrict__ p_rows, int n_rows, const bf16_t* __restrict__ negs,
+                                                            int n_neg, float thres, uint32_t* __restrict__ fixw, int n_rows_pad,
+                                                            const int32_t* __restrict__ row_list, const int32_t* __restrict__ n_list,
+                                                            int32_t* __restrict__ any_out, const int32_t* __restrict__ counter,
+                                                            const int32_t* __restrict__ cand, int cand_cap) {
+  using T = sg::Tile<NKS>;
+  const int n_tiles = (n_neg + 31) >> 5, n_frag = n_rows_pad >> 5;
+  const int any_shift = fix_group_shift(n_tiles);
+  const int lane = threadIdx.x & 63, r = lane & 31, half = lane >> 5;
+  const int n_cand = min(*counter, cand_cap);
+  for (int ci = blockIdx.x * 4 + (threadIdx.x >> 6); ci < n_cand; ci += gridDim.x * 4) {
+    const int code = __builtin_amdgcn_readfirstlane(cand[ci]);
+    const int t = code % n_tiles, fi = (code / n_tiles) % n_frag, z = code / n_tiles / n_frag;
+    const int n_live = row_list ? min(n_list[z], n_rows_pad) : n_rows;
+    const int row = fi * 32 + r;
+    const bool live = row < n_live;
+    const int src_row = row_list ? (live ? row_list[(int64_t)z * n_rows_pad + row] : 0) : row;
+    const IT* src = p_rows + (live ? (int64_t)src_row * T::DIM : 0);
+    const float inv = row_inv_norm<NKS, IT>(src, live, half);
+    bf16x8 frag[NKS];
+    load_norm_frags<NKS, IT>(src, live, half, inv, frag);
+    const bf16_t* nsrc = negs + ((int64_t)z * ((n_neg + 31) & ~31) + t * 32 + r) * T::DIM + 8 * half;
+    f32x16 acc = sg::zero16();
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      const bf16x8 av = *reinterpret_cast<const bf16x8*>(nsrc + ks * 16);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, frag[ks], acc, 0, 0, 0);
+    }
+    uint32_t b = 0;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) b |= acc[g] > thres ? (1u << ((g & 3) + 8 * (g >> 2))) : 0u;
+    uint32_t w = b << (4 * half);
+    w |= __shfl_xor(w, 32, 64);
+    if (half == 0) fixw[((int64_t)z * n_tiles + t) * n_rows_pad + row] = w;
+    if (half == 0 && w != 0u && any_out)
+      atomicOr(reinterpret_cast<unsigned int*>(any_out + (int64_t)z * n_rows_pad + row), 1u << (t >> any_shift));
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // fused forward, false-negative test hoisted out (training path, default)
 // ------------------------------------------------------------------------------------------
 // cos(target, negative) > thres depends on the TARGET ROW, not on the token: at cfg1 every target row is the positive of up
@@ -1349,6 +1604,70 @@ extern "C" int mhr_nce_fix_bits(const void* p_rows, int io_dtype, int64_t n_p_ro
   NKS_SWITCH(nks, LFB_);
 #undef LFB_
   MHR_CHECK_LAUNCH("nce_fix_bits");
+  return MHR_OK;
+}
+
+// workspace of mhr_nce_fix_bits_filtered: [counter, 3 pad] int32 | b_rem [G, n_tiles] f32 | b_full [G, n_tiles] f32 (padded to
+// 16 bytes) | candidates [G * n_rows_pad / 32 * n_tiles] int32 (one slot per (group, row fragment, tile): it cannot overflow)
+static inline int64_t fix_filter_tables_bytes(int n_tiles, int n_groups) {
+  return 16 + ((int64_t)2 * n_groups * n_tiles * 4 + 15) / 16 * 16;
+}
+static inline int64_t fix_filter_cand_cap(int64_t n_p_rows, int n_tiles, int n_groups) {
+  return (int64_t)n_groups * ((n_p_rows + 255) / 256 * 8) * n_tiles;
+}
+extern "C" int64_t mhr_nce_fix_bits_filtered_workspace_bytes(int64_t n_p_rows, int n_neg, int n_groups) {
+  if (n_p_rows <= 0 || n_neg <= 0 || n_groups <= 0) return 0;
+  const int n_tiles = (n_neg + 31) / 32;
+  return fix_filter_tables_bytes(n_tiles, n_groups) + fix_filter_cand_cap(n_p_rows, n_tiles, n_groups) * 4;
+}
+
+extern "C" int mhr_nce_fix_bits_filtered(const void* p_rows, int io_dtype, int64_t n_p_rows, const void* negs, int n_neg, int dim,
+                                         int n_groups, float thres, uint32_t* fix_words, const int32_t* fix_row_list,
+                                         const int32_t* fix_n_rows, int32_t* fix_slot_of_row, int32_t* fix_any,
+                                         void* workspace, int64_t workspace_bytes, void* stream) {
+  MHR_REQUIRE(p_rows && negs && fix_words && workspace, "nce_fix_bits_filtered: null pointer");
+  MHR_REQUIRE((fix_row_list != nullptr) == (fix_n_rows != nullptr) && (fix_n_rows != nullptr) == (fix_slot_of_row != nullptr),
+              "nce_fix_bits_filtered: fix_row_list, fix_n_rows and fix_slot_of_row go together");
+  MHR_REQUIRE(dim == 128 || dim == 256, "nce_fix_bits_filtered: dim=%d unsupported (128/256; mhr_nce_fix_bits takes the smaller ones)", dim);
+  MHR_REQUIRE(n_neg > 0 && n_p_rows > 0 && n_p_rows < (1ll << 31) - 256 && n_groups >= 1 && n_groups <= 65535,
+              "nce_fix_bits_filtered: bad sizes");
+  const int nks = dim / 16;
+  const int n_tiles = (n_neg + 31) / 32, n_rows_pad = (int)((n_p_rows + 255) / 256 * 256);
+  const int64_t cap = fix_filter_cand_cap(n_p_rows, n_tiles, n_groups);
+  MHR_REQUIRE(cap < (1ll << 31), "nce_fix_bits_filtered: %lld (group, row fragment, tile) units do not fit the int32 candidate codes",
+              (long long)cap);
+  MHR_REQUIRE(workspace_bytes >= mhr_nce_fix_bits_filtered_workspace_bytes(n_p_rows, n_neg, n_groups),
+              "nce_fix_bits_filtered: workspace of %lld bytes is too small", (long long)workspace_bytes);
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* counter = (int32_t*)workspace;
+  float* b_rem = (float*)((char*)workspace + 16);
+  float* b_full = b_rem + (int64_t)n_groups * n_tiles;
+  int32_t* cand = (int32_t*)((char*)workspace + fix_filter_tables_bytes(n_tiles, n_groups));
+  int slices = 1;                       // the exhaustive kernel's grid
+  while (slices < 8 && (n_rows_pad / 256) * n_groups * slices < 768 && n_tiles / (slices * 2) >= 16) slices *= 2;
+  const int tps_f = (n_tiles + slices - 1) / slices;
+  int64_t nb_exact = (cap + 3) / 4;     // one wave per candidate at most; 512 workgroups grid-stride over longer lists
+  if (nb_exact > 512) nb_exact = 512;
+#define LFF2_(NKS, IT)                                                                                                   \
+  {                                                                                                                      \
+    hipLaunchKernelGGL((nce_neg_tile_norms_kernel<NKS>), dim3((n_tiles + 3) / 4, n_groups), dim3(256), 0, s,            \
+                       (const bf16_t*)negs, n_neg, b_rem, b_full, counter);                                              \
+    hipLaunchKernelGGL((nce_fix_prefix_kernel<NKS, IT>), dim3(n_rows_pad / 256, slices, n_groups), dim3(256),            \
+                       3 * FIX_SUB * sg::Tile<FIX_KPS>::BYTES, s, (const IT*)p_rows, (int)n_p_rows, (const bf16_t*)negs, n_neg,    \
+                       thres, fix_words, n_rows_pad, tps_f, fix_row_list, fix_n_rows, fix_slot_of_row,                   \
+                       (const float*)b_rem, (const float*)b_full, counter, cand);                                        \
+    hipLaunchKernelGGL((nce_fix_exact_kernel<NKS, IT>), dim3((int)nb_exact), dim3(256), 0, s, (const IT*)p_rows,         \
+                       (int)n_p_rows, (const bf16_t*)negs, n_neg, thres, fix_words, n_rows_pad, fix_row_list,            \
+                       fix_n_rows, fix_any, (const int32_t*)counter, (const int32_t*)cand, (int)cap);                    \
+  }
+#define LFF_(NKS)                                                                                                        \
+  {                                                                                                                      \
+    if (io_dtype == MHR_BF16) LFF2_(NKS, bf16_t) else LFF2_(NKS, float)                                                  \
+  }
+  if (nks == 8) LFF_(8) else LFF_(16)
+#undef LFF_
+#undef LFF2_
+  MHR_CHECK_LAUNCH("nce_fix_bits_filtered");
   return MHR_OK;
 }
 

@@ -208,13 +208,15 @@ struct DmaPieces {
   static constexpr int PW = (PIECES + 3) / 4;
   uint32_t off[PW];        // byte offset of my 16 bytes inside the (unswizzled) source tile, per piece
   int pc[PW];              // piece index (wave-uniform)
-  __device__ __forceinline__ void init(int wave, int lane) {
+  // src_row_bytes: distance between source rows.  Larger than ROW_BYTES when the tile image holds only the leading
+  // columns of wider rows (the prefix pass of the false-negative filter); the fast path stays one SGPR base + off[].
+  __device__ __forceinline__ void init(int wave, int lane, int src_row_bytes = T::ROW_BYTES) {
 #pragma unroll
     for (int i = 0; i < PW; ++i) {
       pc[i] = (wave * PW + i) % PIECES;
       const int pos = pc[i] * 1024 + lane * 16;
       const int row = pos / T::ROW_BYTES, slot = (pos % T::ROW_BYTES) >> 4;
-      off[i] = (uint32_t)(row * T::ROW_BYTES + ((slot ^ T::key(row)) << 4));
+      off[i] = (uint32_t)(row * src_row_bytes + ((slot ^ T::key(row)) << 4));
     }
   }
   template <int K>

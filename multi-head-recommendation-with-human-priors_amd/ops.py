@@ -685,6 +685,7 @@ STREAM_DIMS = (16, 32, 64, 128, 256)      # feature dims of the register-station
 
 
 HOIST_FALSE_NEGATIVE_TEST = os.environ.get("MHR_NCE_HOIST", "1") != "0"
+FILTER_FALSE_NEGATIVE_TEST = os.environ.get("MHR_NCE_FIX_FILTER", "1") != "0"    # 0: the exhaustive bit-table kernel
 
 
 class NceSaved:
@@ -756,8 +757,16 @@ def _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask):
             _ROW_IOTA[key] = (ar[None].expand(G, -1).contiguous(), ar)
         iota_g, iota = _ROW_IOTA[key]
         row_list, _, _, n_list = token_compact(p_row_mask.contiguous(), iota_g, iota, iota, tok_cap=rp_pad)
-    lib.call("mhr_nce_fix_bits", p_rows.data_ptr(), _dt(p_rows), n_p_rows, negs.data_ptr(), n_neg, D, G, float(thres),
-             fix_words.data_ptr(), _ptr(row_list), _ptr(n_list), _ptr(slot_of_row), fix_any.data_ptr(), _stream())
+    if FILTER_FALSE_NEGATIVE_TEST and D >= 128:
+        # prefix filter + exact pass over the survivors (same table, bit for bit); smaller dims keep the exhaustive kernel
+        ws_bytes = lib.load().mhr_nce_fix_bits_filtered_workspace_bytes(n_p_rows, n_neg, G)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        lib.call("mhr_nce_fix_bits_filtered", p_rows.data_ptr(), _dt(p_rows), n_p_rows, negs.data_ptr(), n_neg, D, G, float(thres),
+                 fix_words.data_ptr(), _ptr(row_list), _ptr(n_list), _ptr(slot_of_row), fix_any.data_ptr(), ws.data_ptr(), ws_bytes,
+                 _stream())
+    else:
+        lib.call("mhr_nce_fix_bits", p_rows.data_ptr(), _dt(p_rows), n_p_rows, negs.data_ptr(), n_neg, D, G, float(thres),
+                 fix_words.data_ptr(), _ptr(row_list), _ptr(n_list), _ptr(slot_of_row), fix_any.data_ptr(), _stream())
     return fix_words, fix_any, slot_of_row, (row_list, n_list)
 
 
