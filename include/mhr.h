@@ -68,7 +68,11 @@ int mhr_embedding_gather_fwd(const float* table, int64_t n_rows, int dim,
  * dim % 4 == 0, dim <= 2048; ids outside [0, n_rows) are clamped and counted (mhr_bad_id_count). */
 int mhr_embedding_gather_step(const float* table, int64_t n_rows, int dim, const int64_t* ids, int64_t n_ids,
                               int64_t n_item_ids, float* rows_out, const float* pos_table, int seq_len, int window_len,
-                              float* x_out, void* neg_out, float* neg_norms, void* stream);
+                              float* x_out, void* neg_out, float* neg_norms, const int32_t* row_of, const int32_t* src_of,
+                              int capacity, void* stream);
+/* row_of / src_of (both or neither; the batch's maps of mhr_seq_pack_maps) + capacity: x_out is the PACKED encoder input
+ * [capacity, dim] - position (b, l) goes to row row_of[b seq_len + l] (padding positions are not written), the rows behind the
+ * batch's valid count (src_of < 0) are written as zeros by the same launch.  Bitwise mhr_rows_gather_masked of the window form. */
 
 /* Dense embedding backward (ATen embedding_dense_backward): grad_table[ids[r],:] += grad_rows[r,:]
  * with float atomics.  grad_table [n_rows, dim] f32 must be zeroed by the caller. */
@@ -90,8 +94,20 @@ int mhr_embedding_scatter_add_bwd(const void* grad_rows, int grad_dtype, const i
 int mhr_sparse_rows_segment_sum(const int64_t* sorted_ids, const int64_t* perm, int64_t n_ids,
                                 const void* grad_a, int a_dtype, int64_t n_a,
                                 const void* grad_b, int b_dtype, int64_t n_b,
-                                const float* x_grad, int seq_len, int window_len,
+                                const float* x_grad, int seq_len, int window_len, const int32_t* x_row_of,
                                 float* out_rows, int32_t* row_slot, int64_t n_rows, int dim, void* stream);
+/* x_row_of (optional, [n_a / window_len, seq_len] int32: row_of of mhr_seq_pack_maps): x_grad holds the PACKED rows of the valid
+ * positions ([capacity, dim]); position (b, l) reads row x_row_of[b seq_len + l], a padding position (-1) adds nothing. */
+
+/* The packed encoder input's gradient d_x [capacity, dim] f32 read through row_of [B L] (no copy back to the windows):
+ *   mhr_pos_grad_packed: out[l, :] += sum_b d_x[row_of[b L + l], :] - the position table's gradient (hstu.py:640-643's backward),
+ *     one fixed summation order, no atomics;
+ *   mhr_window_rows_add_packed: out[b W + l, :] = rows[b W + l, :] + d_x[row_of[b L + l], :] (l < L, valid positions; the other
+ *     rows are copied) - the item windows' gradient rows with the input-side gradient folded in, in a buffer of the caller's own
+ *     (data-parallel / accumulating steps). */
+int mhr_pos_grad_packed(const float* d_x, const int32_t* row_of, int B, int L, int dim, float* out, void* stream);
+int mhr_window_rows_add_packed(const float* rows, int64_t n_rows, int window_len, int seq_len, const float* d_x,
+                               const int32_t* row_of, int dim, float* out, void* stream);
 
 /* Dense AdamW over an embedding table whose gradient is given sparsely (trainer.py:292-299 semantics:
  * every row is updated every step, untouched rows with g = 0).  For each row: slot = row_slot[row];
@@ -332,14 +348,21 @@ int mhr_softmax_attn_bwd(const void* q, const void* k, const void* v, int64_t ro
  * ---------------------------------------------------------------------------------------- */
 int mhr_token_compact(const uint8_t* mask, const int32_t* q_all, const int32_t* p_all, const int32_t* o_all,
                       int n_groups, int n_slots, int tok_cap, int32_t* q_idx, int32_t* p_idx, int32_t* o_idx,
-                      int32_t* n_tok, int32_t* scratch, int32_t* tok_of_slot, void* stream);
+                      int32_t* n_tok, int32_t* scratch, int32_t* tok_of_slot, const int32_t* row_of, int seq_len,
+                      int n_heads, int head_stride, void* stream);
 /* tok_of_slot (may be NULL) [n_groups, n_slots] int32: the inverse map - position of a live slot in its group's list,
- * -1 for slots that are not live (or fell beyond tok_cap). */
+ * -1 for slots that are not live (or fell beyond tok_cap).
+ * row_of (may be NULL) [B seq_len] int32, the batch's map of mhr_seq_pack_maps: PACKED head rows.  q_all then holds the window
+ * form (b n_heads + h) seq_len + l and the list receives q = h head_stride + row_of[b seq_len + l] - head rows laid out
+ * [n_heads, head_stride, dim] over the packed positions (head_stride >= the capacity of the maps).  Slot order, p_idx, o_idx, n_tok
+ * and tok_of_slot are those of the window form.  A live slot without a packed row is counted into mhr_bad_id_count (and reads
+ * row 0 of its head). */
 
 /* ------------------------------------------------------------------------------------------
  * Decoding heads after their one concatenated GEMM (model/llm_heads.py:5-40, stacked and permuted by hstu.py:665-667):
  *   out[b, h, l, :] = x[b, l, :] + silu(z[b, l, h, :]),  x [n_tok, dim] f32 (n_tok = B seq_len), z [n_tok, n_heads dim] bf16,
  *   out [B, n_heads, seq_len, dim] f32 - the layout the loss reads.  Backward: dz = d_out silu'(z) (bf16), dx = sum_h d_out (f32).
+ * On packed rows (mhr_seq_pack_maps) the batch is one sequence: n_tok = seq_len = capacity, out [n_heads, capacity, dim].
  * ---------------------------------------------------------------------------------------- */
 int mhr_heads_residual_fwd(const float* x, const void* z_bf16, float* out, int64_t n_tok, int seq_len, int n_heads,
                            int dim, void* stream);

@@ -201,48 +201,68 @@ class HSTU(MultiHeadDecoding, BaseModel):
         mask, unless `switch_last_only`) does read them - and sends gradient into them - so those models keep every row."""
         return getattr(self, "prior_switch", None) is None or bool(getattr(self, "switch_last_only", False))
 
-    def _encode(self, x, key_valid, training=None, want_bf16=False):
+    def _pack_plan(self, key_valid, B, L, D):
+        """(capacity, cu_rows, src_of, row_of) when the encoder of this batch runs on PACKED rows, else None.
+        The batch carries a static capacity for its valid positions (`_mhr_rows_cap` on the mask: a bucketed count the loader
+        knows on the host) - the layers then run over the valid rows only, back to back in a [capacity, D] buffer
+        (csrc/rows_pack.hip), the attention addresses the sequences through cu_rows.  Same condition as the dead rows: nothing
+        may read the hidden states of padding positions.  Data parallel: the capacity is part of the batch signature the step
+        graphs are keyed on, and every rank must capture and replay in the same steps (a capture issues no collective) - the
+        loaders must hand all ranks the SAME capacity for a step (the maximum over the ranks; bench.py does that).
+        The maps depend on the mask only: `forward` builds them in front of the embedding gather and the early loss stages."""
+        from mhr_amd import ops
+        n = len(self._hstu._attention_layers)
+        if ops.SEQ_LAYOUT and n and getattr(key_valid, "_mhr_layout", None) is None:
+            key_valid._mhr_layout = ops.attn_seq_layout(key_valid, B, L)     # front padding: the layers skip the dead blocks
+        lay = getattr(key_valid, "_mhr_layout", None)
+        cap = getattr(key_valid, "_mhr_rows_cap", None)
+        if not (cap is not None and ops.PACK_ROWS and n and lay is not None and self._dead_rows_allowed() and 0 < int(cap) < B * L
+                and D % 8 == 0 and self._packable(L)):
+            return None
+        cap = int(cap)
+        cu, src_of, row_of, overflow = ops.seq_pack_maps(key_valid, B, L, cap)
+        # a capacity below the batch's valid positions would silently drop rows: the first host-issued steps at a capacity
+        # read the count back (a captured step cannot, and later steps trust the loader)
+        seen = self.__dict__.setdefault("_pack_checked", {})
+        if not torch.cuda.is_current_stream_capturing() and seen.get(cap, 0) < 4:
+            seen[cap] = seen.get(cap, 0) + 1
+            if int(overflow.item()) != 0:
+                raise RuntimeError(f"packed encoder rows: the batch has {int(overflow.item())} valid positions, "
+                                   f"its capacity hint (_mhr_rows_cap) says {cap}")
+        return cap, cu, src_of, row_of
+
+    def _encode(self, x, key_valid, training=None, want_bf16=False, plan=None):
         """x [B,L,D] fp32, key_valid [B,L] uint8 -> [B,L,D] fp32 (reference hstu.py:221-328); want_bf16: (out, its bf16 copy -
-        the operand of the decoding heads' GEMM, written by the last residual add's own pass)."""
+        the operand of the decoding heads' GEMM, written by the last residual add's own pass).
+        plan (`_pack_plan` of this mask, made by the caller): x IS the packed encoder input [capacity, D] and the output stays
+        packed ([capacity, D], zero rows behind the valid count) - no window-shaped activation on the way."""
         from mhr_amd import ops
         from REC.model.hstu_functional import (AddCastFn, AddLayerNormFn, HSTUCoreFn, LayerNormFn, LayerNormResidualFn, SplitKLinearFn,
                                                WeightGradStack, ROWS_GEMM, _rows_gemm_pays)
-        B, L, D = x.shape
-        x2 = x.reshape(B * L, D)
+        packed_io = plan is not None
+        B, L = key_valid.shape
+        D = x.shape[-1]
+        x2 = x.reshape(-1, D)
         training = self.training if training is None else training
         p = self._linear_dropout_rate if training else 0.0
         layers = self._hstu._attention_layers
         n = len(layers)
-        if ops.SEQ_LAYOUT and n and getattr(key_valid, "_mhr_layout", None) is None:
-            key_valid._mhr_layout = ops.attn_seq_layout(key_valid, B, L)     # front padding: the layers skip the dead blocks
+        if plan is None:
+            plan = self._pack_plan(key_valid, B, L, D)
         lay = getattr(key_valid, "_mhr_layout", None)
         key_valid._mhr_dead_ok = self._dead_rows_allowed()
         # rows in front of a sequence's first valid key: the layers' row-wise kernels do not load them (zeros in, zeros out)
         dead = (lay[2], L) if (ops.DEAD_ROWS and lay is not None and len(lay) > 2 and self._dead_rows_allowed()) else None
-        # PACKED rows: the batch carries a static capacity for its valid positions (`_mhr_rows_cap` on the mask: a bucketed count
-        # the loader knows on the host) - the layers then run over the valid rows only, back to back in a [capacity, D] buffer
-        # (csrc/rows_pack.hip), the attention addresses the sequences through cu_rows.  Same condition as the dead rows: nothing
-        # may read the hidden states of padding positions.  Data parallel: the capacity is part of the batch signature the step
-        # graphs are keyed on, and every rank must capture and replay in the same steps (a capture issues no collective) - the
-        # loaders must hand all ranks the SAME capacity for a step (the maximum over the ranks; bench.py does that).
-        cap = getattr(key_valid, "_mhr_rows_cap", None)
+        # PACKED rows (`_pack_plan`): the layers run over the valid positions only
         pack = None
-        if (cap is not None and ops.PACK_ROWS and n and lay is not None and self._dead_rows_allowed() and 0 < int(cap) < B * L
-                and D % 8 == 0 and self._packable(L)):
+        if plan is not None:
             from REC.model.hstu_functional import MoveRowsFn
-            cap = int(cap)
-            cu, src_of, row_of, overflow = ops.seq_pack_maps(key_valid, B, L, cap)
-            # a capacity below the batch's valid positions would silently drop rows: the first host-issued steps at a capacity
-            # read the count back (a captured step cannot, and later steps trust the loader)
-            seen = self.__dict__.setdefault("_pack_checked", {})
-            if not torch.cuda.is_current_stream_capturing() and seen.get(cap, 0) < 4:
-                seen[cap] = seen.get(cap, 0) + 1
-                if int(overflow.item()) != 0:
-                    raise RuntimeError(f"packed encoder rows: the batch has {int(overflow.item())} valid positions, "
-                                       f"its capacity hint (_mhr_rows_cap) says {cap}")
+            cap, cu, src_of, row_of = plan
             pack = (src_of, row_of)
-            x2 = MoveRowsFn.apply(x2, src_of, row_of)                      # [cap, D]
-            kv_w = key_valid
+            if not packed_io:
+                x2 = MoveRowsFn.apply(x2, src_of, row_of)                  # [cap, D]
+            elif tuple(x2.shape) != (cap, D):
+                raise RuntimeError(f"_encode: a packed encoder input must be [{cap}, {D}], got {tuple(x2.shape)}")
             key_valid = self._ones_u8(cap, x.device)
             key_valid._mhr_layout = (None, lay[1], None, cu)                # sequences longest first, addressed through cu_rows
             key_valid._mhr_dead_ok = False
@@ -283,11 +303,15 @@ class HSTU(MultiHeadDecoding, BaseModel):
                 x2, xn = AddLayerNormFn.apply(x2, y, layers[i + 1]._eps, sl(stack and stack.xn, i + 1), sl(stack and stack.dy, i), dead)
             elif want_bf16 and y.dtype == torch.bfloat16 and x2.numel() % 8 == 0:
                 x2, x16 = AddCastFn.apply(x2, y, sl(stack and stack.dy, i))
+                if packed_io:
+                    return x2, x16
                 if pack is not None:                        # back to the windows: padding positions read as zeros
                     x2, x16 = MoveRowsFn.apply(x2, pack[1], pack[0]), MoveRowsFn.apply(x16, pack[1], pack[0])
                 return x2.view(B, L, D), x16.view(B, L, D)
             else:
                 x2 = torch.add(x2, y)           # fp32 + bf16 -> fp32 in one kernel
+        if packed_io:
+            return (x2, None) if want_bf16 else x2
         if pack is not None:
             x2 = MoveRowsFn.apply(x2, pack[1], pack[0])
         return (x2.view(B, L, D), None) if want_bf16 else x2.view(B, L, D)
@@ -341,9 +365,23 @@ class HSTU(MultiHeadDecoding, BaseModel):
         fused_pos = isinstance(self.item_id_proj_tower, nn.Identity)
         # the negative pools: gathered and L2-normalised in one pass (bf16 out) when the table rows are what the loss sees
         fused_negs = fused_pos and FUSED_NEG_GATHER and torch.is_grad_enabled() and not self.dense_embedding_grad
+        key_valid = mask[:, :L].to(torch.uint8).contiguous()
+        if getattr(user_mask, "_mhr_rows_cap", None) is not None:  # the loader's static bound on the batch's valid positions (packed rows)
+            key_valid._mhr_rows_cap = user_mask._mhr_rows_cap
+        # PACKED step (ops.PACK_HEADS, when the encoder packs this batch anyway): the gather writes the encoder input as the
+        # [capacity, D] rows of the valid positions, the decoding heads run on the packed encoder output ([H, capacity, D] head
+        # rows) and the token lists name those rows - nothing between the gather and the loss is window-shaped.  The row maps
+        # depend on the mask only: made here, in front of the gather and of the early loss stages on the side stream.
+        # (The prior switch reads hidden states by window position: those models keep the window form behind the encoder.)
+        from mhr_amd import ops
+        plan_rows = None
+        if ops.PACK_HEADS and fused_negs and getattr(self, "prior_switch", None) is None:
+            plan_rows = self._pack_plan(key_valid, B, L, D)
+        packed = None if plan_rows is None else (plan_rows[3], plan_rows[0])          # (row_of, capacity)
         rows_items, rows_negs, x = EmbeddingGatherFn.apply(self.item_embedding.weight,
                                               self.position_embedding.weight if fused_pos else None, ids_all,
-                                              n_item_ids, L, L + P, self, fused_negs)
+                                              n_item_ids, L, L + P, self, fused_negs,
+                                              None if plan_rows is None else (plan_rows[3], plan_rows[2], plan_rows[0]))
         if not fused_pos:
             rows_all = self.item_id_proj_tower(torch.cat([rows_items, rows_negs]))
             rows_items, rows_negs = rows_all[:n_item_ids], rows_all[n_item_ids:]
@@ -357,9 +395,6 @@ class HSTU(MultiHeadDecoding, BaseModel):
             negs_pools = L2NormFn.apply(rows_negs.contiguous(), self if fused_pos else None)
         negs_pools = negs_pools.view(len(pools), n_pool, D)
 
-        key_valid = mask[:, :L].to(torch.uint8).contiguous()
-        if getattr(user_mask, "_mhr_rows_cap", None) is not None:  # the loader's static bound on the batch's valid positions (packed rows)
-            key_valid._mhr_rows_cap = user_mask._mhr_rows_cap
         # everything of the loss that waits for nothing the encoder makes (token lists, row maps, the false-negative bit table of
         # the target rows, the accumulators of the loss backward, the id sort of the embedding backward) runs UNDERNEATH the
         # encoder on a second stream: some fifty few-microsecond launches and one 0.2 ms MFMA kernel on 104 workgroups that
@@ -368,7 +403,8 @@ class HSTU(MultiHeadDecoding, BaseModel):
         capturing = torch.cuda.is_current_stream_capturing()
         segs = getattr(self, "_graph_segments", None) if capturing else None
         if early_prep:
-            stages = self._early_loss_stages(st, pools, mask, pos_tags, e_rows, negs_pools, n_q_rows=B * self.medusa_num_heads * L)
+            stages = self._early_loss_stages(st, pools, mask, pos_tags, e_rows, negs_pools, packed=packed,
+                                             n_q_rows=self.medusa_num_heads * (B * L if packed is None else packed[1]))
             stages.insert(0, self._clamp_logit_scale)            # (read by the loss kernels only: behind the join)
             stages.append(lambda: self._presort_ids(ids_all if self._dp_ids is None else self._dp_ids))
 
@@ -383,7 +419,7 @@ class HSTU(MultiHeadDecoding, BaseModel):
             # single-stream graph, which ROCm launches with one cheap host call; a graph with a forked branch cost 2.4 ms of
             # host time per replay, measured)
             segs.side_branch(run_stages)
-            out, out16 = self._encode(x, key_valid, want_bf16=True)
+            out, out16 = self._encode(x, key_valid, want_bf16=True, plan=plan_rows)
             segs.join()
         elif stages and not capturing:
             # host-issued steps: a second stream forked here and joined in front of the heads; the encoder's launches go first
@@ -392,15 +428,19 @@ class HSTU(MultiHeadDecoding, BaseModel):
                 self._side_stream = torch.cuda.Stream(device=items.device)
             side = self._side_stream
             side.wait_stream(torch.cuda.current_stream())        # the fork: everything up to here (rows, negatives) is visible
-            out, out16 = self._encode(x, key_valid, want_bf16=True)
+            out, out16 = self._encode(x, key_valid, want_bf16=True, plan=plan_rows)
             with torch.cuda.stream(side):
                 run_stages()
             torch.cuda.current_stream().wait_stream(side)
         else:                                                    # (somebody else's capture: one stream, the stages in line)
             run_stages()
-            out, out16 = self._encode(x, key_valid, want_bf16=True)
+            out, out16 = self._encode(x, key_valid, want_bf16=True, plan=plan_rows)
         plan, early = st.get("plan"), st.get("early")
-        return self._multihead_loss(out, e_rows, negs_pools, pools, mask, pos_tags, plan=plan, early=early, out_bf16=out16)
+        if packed is not None:                  # "one sequence of `capacity` rows": the heads then write [1, H, capacity, D]
+            out = out.view(1, packed[1], D)
+            out16 = None if out16 is None else out16.view(1, packed[1], D)
+        return self._multihead_loss(out, e_rows, negs_pools, pools, mask, pos_tags, plan=plan, early=early, out_bf16=out16,
+                                    packed=packed)
 
     def _presort_ids(self, ids_all):
         """The id sort and the zeroed row buffer of the sparse embedding backward (EmbeddingGatherFn.backward) depend on the

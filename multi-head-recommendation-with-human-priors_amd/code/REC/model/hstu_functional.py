@@ -408,17 +408,24 @@ class EmbeddingGatherFn(Function):
     """
 
     @staticmethod
-    def forward(ctx, table, pos_table, ids_all, n_item_ids, L, window, holder, negs_elsewhere=False):
+    def forward(ctx, table, pos_table, ids_all, n_item_ids, L, window, holder, negs_elsewhere=False, pack=None):
         D = table.shape[1]
         n_neg = ids_all.numel() - n_item_ids
         ctx.save_for_backward(ids_all)
         ctx.meta = (n_item_ids, L, window, holder, table.shape[0], D)
+        # pack = (row_of, src_of, capacity) (ops.seq_pack_maps; one-launch form only): x is the PACKED encoder input
+        # [capacity, D], and its gradient arrives packed - the backward reads it through row_of, no copy to the windows either way
+        ctx.row_of = None
+        if pack is not None:
+            if not (negs_elsewhere and pos_table is not None):
+                raise RuntimeError("EmbeddingGatherFn: the packed encoder input needs the one-launch gather (position table, fused negatives)")
+            ctx.row_of = pack[0]
         if negs_elsewhere and pos_table is not None:
             # ONE launch (mhr_embedding_gather_step): item windows as fp32 rows + position-added x, the negative pools gathered
             # AND L2-normalised to bf16 with no fp32 copy of their rows.  The normalised pools enter autograd through
             # GatherL2NormFn; this Function's second output is a memory-less stand-in for the pools' raw rows - the gradient
             # GatherL2NormFn returns for it arrives here as d_negs, exactly like the gradient of real rows would
-            rows, x, negs_n, norms = ops.embedding_gather_step(table, pos_table, ids_all, n_item_ids, L, window)
+            rows, x, negs_n, norms = ops.embedding_gather_step(table, pos_table, ids_all, n_item_ids, L, window, pack=pack)
             holder._gathered_negs = (negs_n, norms)           # picked up by GatherL2NormFn.forward right behind this call
             return rows, torch.zeros((), dtype=torch.float32, device=table.device).expand(n_neg, D), x
         rows = torch.empty(ids_all.numel(), D, dtype=torch.float32, device=table.device)
@@ -443,9 +450,17 @@ class EmbeddingGatherFn(Function):
         early_shared = getattr(holder, "_shared_pending", None) is not None        # (data parallel: the negatives' gradient is elsewhere)
         if n_neg_ids and not early_shared:
             d_negs = d_negs.contiguous() if d_negs is not None else torch.zeros(n_neg_ids, D, device=dev)
-        d_x = d_x.contiguous() if (d_x is not None and d_x.dim() == 3) else None
+        row_of = ctx.row_of
+        d_x = d_x.contiguous() if (d_x is not None and d_x.dim() == (3 if row_of is None else 2)) else None
         d_pos = None
-        if d_x is not None:
+        if d_x is not None and row_of is not None:           # packed d_x [capacity, D]: summed over the batch through the map
+            pos = holder.position_embedding.weight
+            pg = pos.grad if getattr(pos, "_mhr_direct_grad", False) else None
+            if pg is not None and pg.is_contiguous() and pg.dtype == torch.float32 and pg.data_ptr() % 16 == 0:
+                ops.pos_grad_packed(d_x, row_of, n_item_ids // window, L, pg)
+            else:
+                d_pos = ops.pos_grad_packed(d_x, row_of, n_item_ids // window, L, torch.zeros(pos.shape, dtype=torch.float32, device=dev))
+        elif d_x is not None:
             pos = holder.position_embedding.weight
             pg = pos.grad if getattr(pos, "_mhr_direct_grad", False) else None
             if pg is not None and pg.is_contiguous() and pg.dtype == torch.float32 and (L * D) % 8 == 0 and pg.data_ptr() % 16 == 0:
@@ -460,7 +475,7 @@ class EmbeddingGatherFn(Function):
                 ops.embedding_scatter_add(d_negs, ids_all[n_item_ids:].contiguous(), gt)
             if d_x is not None:
                 ops.embedding_scatter_add(d_x.view(-1, D), ids_all[:n_item_ids].view(-1, window)[:, :L].contiguous().view(-1), gt)
-            return gt, d_pos, None, None, None, None, None, None
+            return gt, d_pos, None, None, None, None, None, None, None
         if holder._row_slot is None or holder._row_slot.numel() != n_rows:
             holder._row_slot = torch.full((n_rows,), -1, dtype=torch.int32, device=dev)
         from mhr_amd import distributed as dist_
@@ -475,22 +490,29 @@ class EmbeddingGatherFn(Function):
                 d_rows = d_items
             else:
                 d_rows = torch.cat([d_items, d_negs])
-            if d_x is not None:
+            if d_x is not None and row_of is not None:
+                # (never in place: without local negatives d_rows IS the incoming gradient tensor)
+                if d_rows is d_items:
+                    d_rows = ops.window_rows_add_packed(d_items, window, L, d_x, row_of)
+                else:                                         # (d_rows is this backward's own concatenation)
+                    ops.window_rows_add_packed(d_items, window, L, d_x, row_of, out=d_rows[:n_item_ids])
+            elif d_x is not None:
                 d_rows[:n_item_ids].view(-1, window, D)[:, :L] += d_x
             if holder._pending_rows is None:
                 holder._pending_rows = []
             holder._pending_rows.append((ids_all, d_rows, n_item_ids, shared))
             holder.sparse_grad = None
-            return None, d_pos, None, None, None, None, None, None
+            return None, d_pos, None, None, None, None, None, None, None
         pre, holder._presorted = getattr(holder, "_presorted", None), None
         if pre is not None and pre[0].data_ptr() == ids_all.data_ptr() and pre[0].numel() == ids_all.numel():        # sorted (and the row buffer zeroed) early, underneath the encoder forward
             _, sorted_ids, perm, out_rows = pre
         else:
             sorted_ids, perm = torch.sort(ids_all)
             out_rows = torch.zeros(ids_all.numel(), D, dtype=torch.float32, device=dev)
-        ops.sparse_rows_segment_sum(sorted_ids, perm, d_items, d_negs if n_neg_ids else None, d_x, L, window, out_rows, holder._row_slot)
+        ops.sparse_rows_segment_sum(sorted_ids, perm, d_items, d_negs if n_neg_ids else None, d_x, L, window, out_rows, holder._row_slot,
+                                    x_row_of=row_of if d_x is not None else None)
         holder.sparse_grad = SparseRowGrad(sorted_ids, out_rows, holder._row_slot, n_rows)
-        return None, d_pos, None, None, None, None, None, None
+        return None, d_pos, None, None, None, None, None, None, None
 
 
 def begin_pending_rows(holder):

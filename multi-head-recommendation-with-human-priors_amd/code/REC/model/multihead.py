@@ -278,21 +278,28 @@ class MultiHeadDecoding:
             self._tok_cache[key] = all(a.isdisjoint(b) for i, a in enumerate(sets) for b in sets[i + 1:])
         return self._tok_cache[key]
 
-    def _token_lists(self, valid_g, head_for_p, q_all=None):
-        """Ordered compaction of the live (group, slot) pairs of valid_g [G,B,L,P]: (share, q_idx, p_idx, o_idx, n_tok, window)."""
+    def _token_lists(self, valid_g, head_for_p, q_all=None, packed=None):
+        """Ordered compaction of the live (group, slot) pairs of valid_g [G,B,L,P]: (share, q_idx, p_idx, o_idx, n_tok, window).
+        packed = (row_of, capacity) (ops.seq_pack_maps of the batch; static query rows only): the head rows are laid out
+        [H, capacity, D] over the packed positions and q_idx names h * capacity + row_of[b L + l]; the rest is unchanged."""
         from mhr_amd import ops
         G, B, L, P = valid_g.shape
         n_slots = B * P * L
         q_static, p_all, o_all = self._token_tables(B, valid_g.device, head_for_p)
         q_all = q_static if q_all is None else q_all          # (a model may pick the query row per token itself: ComiRec)
         share = P > 1 and q_all is q_static      # the P offsets of a position share their query row (csrc/nce_shared.hip)
+        if packed is not None:
+            if q_all is not q_static:
+                raise ValueError("packed head rows need the static query-row table")
+            packed = (packed[0], L, self.medusa_num_heads, int(packed[1]))
         if share:
-            q_idx, p_idx, o_idx, n_tok, tos = ops.token_compact(valid_g.reshape(G, n_slots), q_all, p_all, o_all, slot_map=True)
+            q_idx, p_idx, o_idx, n_tok, tos = ops.token_compact(valid_g.reshape(G, n_slots), q_all, p_all, o_all, slot_map=True,
+                                                                packed=packed)
             return share, q_idx, p_idx, o_idx, n_tok, (tos, L, P)
-        q_idx, p_idx, o_idx, n_tok = ops.token_compact(valid_g.reshape(G, n_slots), q_all, p_all, o_all)
+        q_idx, p_idx, o_idx, n_tok = ops.token_compact(valid_g.reshape(G, n_slots), q_all, p_all, o_all, packed=packed)
         return share, q_idx, p_idx, o_idx, n_tok, None
 
-    def _early_loss_stages(self, st, pools, mask, pos_tags, e_rows, negs_pools, n_q_rows=None):
+    def _early_loss_stages(self, st, pools, mask, pos_tags, e_rows, negs_pools, n_q_rows=None, packed=None):
         """The batch-only half of the grouped loss as a list of stages (callables, run in order on ONE stream - HSTU.forward
         runs them on a second stream, one between every two encoder layers): the loss plan, the token lists of its groups and
         the stages of `ops.nce_shared_prepare_stages` (row maps, false-negative bit table, normalised targets, accumulators) -
@@ -306,7 +313,7 @@ class MultiHeadDecoding:
 
         def tokens():
             pl = st["plan"]
-            tk = self._token_lists(pl["valid_g"], pl["head_for_p_g"])
+            tk = self._token_lists(pl["valid_g"], pl["head_for_p_g"], packed=packed)
             st["early"] = dict(tokens=tk, prep=None)
             if tk[0] and pl["slots"] == list(range(negs_pools.shape[0])):          # negs_g IS negs_pools: same memory on both streams
                 prep, more = ops.nce_shared_prepare_stages(tk[1], tk[2], tk[4], e_rows.detach(), negs_pools.detach().contiguous(),
@@ -319,7 +326,7 @@ class MultiHeadDecoding:
         return stages
 
     def _grouped_loss(self, head_rows, e_rows, negs_g, valid_g, head_for_p, log_group, p_row_mask=None, q_all=None, ihn_beta=0.0,
-                      early=None, bucket_weight=None, n_segments=1):
+                      early=None, bucket_weight=None, n_segments=1, packed=None):
         """Sampled-softmax loss of G (token mask, negative pool) groups in ONE fused launch per kernel.
         valid_g [G,B,L,P] bool (offset fastest), negs_g [G,n_neg,D] bf16, head_for_p [G,P].  Returns (mean loss per (group, offset)
         [G,P] fp32, logs of `log_group` or None).  No host sync: tokens are compacted by scatter at fixed capacity
@@ -328,7 +335,7 @@ class MultiHeadDecoding:
         from REC.model.hstu_functional import NceLossFn
         G, B, L, P = valid_g.shape
         from mhr_amd import ops
-        share, q_idx, p_idx, o_idx, n_tok, window = early["tokens"] if early is not None else self._token_lists(valid_g, head_for_p, q_all)
+        share, q_idx, p_idx, o_idx, n_tok, window = early["tokens"] if early is not None else self._token_lists(valid_g, head_for_p, q_all, packed)
         cap = q_idx.shape[1]
         want_logs = log_group is not None
         logs = {} if want_logs else None
@@ -409,11 +416,15 @@ class MultiHeadDecoding:
                     log_group=max(i for i, g in enumerate(groups) if g[3] == 'nce' or g[4] == 0),
                     p_row_mask=rows_g.reshape(len(groups), -1).contiguous())
 
-    def _multihead_loss(self, out, e_rows, negs_pools, pools, mask, pos_tags, plan=None, early=None, out_bf16=None):
+    def _multihead_loss(self, out, e_rows, negs_pools, pools, mask, pos_tags, plan=None, early=None, out_bf16=None, packed=None):
         """Everything of the training forward after the sequence encoder (reference hstu.py:648-872 / hllm.py:506-763).
         out [B,L,D] fp32 encoder output; e_rows [B*(L+P), D] fp32 target-item rows; negs_pools [len(pools), n_pool, D]
         bf16 L2-normalised; mask [B,L+P] bool; pos_tags [B,L+P,C]; plan / early: the results of `_early_loss_stages(...)` when the
-        caller built them before the encoder ran."""
+        caller built them before the encoder ran.  packed = (row_of, capacity): out is the PACKED encoder output [1, capacity, D]
+        (the valid positions of the batch back to back), the head rows are [H, capacity, D] and the token lists name them
+        through row_of (`_token_lists`); models without a prior switch only."""
+        if packed is not None and (self.prior_switch is not None or tuple(out.shape[:2]) != (1, int(packed[1]))):
+            raise ValueError("_multihead_loss: packed head rows need out [1, capacity, D] and no prior switch")
         dev = out.device
         B = out.shape[0]
         L, P, D = self.max_seq_length, self.pred_len, self._head_dim
@@ -436,7 +447,7 @@ class MultiHeadDecoding:
         # the mean per offset, its weighting, the total and the log values (the reference's per-head / per-segment sums,
         # hstu.py:700-721, 836-858) come out of ONE launch behind the loss kernels; the log values are views of its output
         (total, red), logs = self._grouped_loss(head_rows, e_rows, negs_g.contiguous(), valid_g, head_for_p_g, log_group,
-                                                p_row_mask, early=early, bucket_weight=self._tok_cache[gw], n_segments=S)
+                                                p_row_mask, early=early, bucket_weight=self._tok_cache[gw], n_segments=S, packed=packed)
         seg_all = red[G * P:G * P + G * S].view(G, S)
         g_tot = red[G * P + G * S:G * P + G * S + G]
         seg_tot = seg_all[0] if (additive or groups[0][3] == 'nce') else red[G * P + G * S + G:]

@@ -67,7 +67,9 @@ __global__ __launch_bounds__(256) void gather_step_kernel(const float* __restric
                                                           const int64_t* __restrict__ ids, int64_t n_ids, int64_t n_item_ids,
                                                           float* __restrict__ out, const float* __restrict__ pos, int seq_len,
                                                           int window_len, float* __restrict__ x_out, bf16_t* __restrict__ neg_out,
-                                                          float* __restrict__ neg_norms, int grid_items) {
+                                                          float* __restrict__ neg_norms, int grid_items,
+                                                          const int32_t* __restrict__ row_of, const int32_t* __restrict__ src_of,
+                                                          int capacity) {
   const int lane = threadIdx.x & 63;
   if ((int)blockIdx.x < grid_items) {
     const int64_t wave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -97,10 +99,20 @@ __global__ __launch_bounds__(256) void gather_step_kernel(const float* __restric
           const int64_t b = r / window_len;
           const int l = (int)(r - b * window_len);
           if (l < seq_len) {
-            const f32x4 p = *reinterpret_cast<const f32x4*>(pos + (int64_t)l * dim + c);
-            *reinterpret_cast<f32x4*>(x_out + (b * seq_len + l) * dim + c) = v[u] + p;
+            // packed encoder input: the valid positions back to back (row_of: mhr_seq_pack_maps), padding positions have no row
+            const int64_t xr = row_of ? (int64_t)row_of[b * seq_len + l] : b * seq_len + l;
+            if (xr >= 0) {
+              const f32x4 p = *reinterpret_cast<const f32x4*>(pos + (int64_t)l * dim + c);
+              *reinterpret_cast<f32x4*>(x_out + xr * dim + c) = v[u] + p;
+            }
           }
         }
+      }
+    }
+    if (src_of) {                                            // the rows between the batch's valid count and the capacity: zeros
+      for (int64_t r = wave; r < capacity; r += n_waves) {
+        if (src_of[r] >= 0) continue;
+        for (int c = lane * 4; c < dim; c += 256) *reinterpret_cast<f32x4*>(x_out + r * dim + c) = f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
     return;
@@ -149,20 +161,24 @@ __global__ __launch_bounds__(256) void gather_step_kernel(const float* __restric
 
 extern "C" int mhr_embedding_gather_step(const float* table, int64_t n_rows, int dim, const int64_t* ids, int64_t n_ids,
                                          int64_t n_item_ids, float* rows_out, const float* pos_table, int seq_len, int window_len,
-                                         float* x_out, void* neg_out, float* neg_norms, void* stream) {
+                                         float* x_out, void* neg_out, float* neg_norms, const int32_t* row_of,
+                                         const int32_t* src_of, int capacity, void* stream) {
   MHR_REQUIRE(table && ids && rows_out && pos_table && x_out, "embedding_gather_step: null pointer");
   MHR_REQUIRE(dim > 0 && dim % 4 == 0 && dim <= 2048, "embedding_gather_step: dim=%d unsupported (multiple of 4, <= 2048)", dim);
   MHR_REQUIRE(n_rows > 0 && n_item_ids >= 0 && n_ids >= n_item_ids && window_len > 0 && seq_len > 0 && seq_len <= window_len &&
               n_item_ids % window_len == 0, "embedding_gather_step: bad sizes (n_ids=%lld n_item_ids=%lld window=%d seq=%d)",
               (long long)n_ids, (long long)n_item_ids, window_len, seq_len);
   MHR_REQUIRE(n_ids == n_item_ids || (neg_out && neg_norms), "embedding_gather_step: negative ids without neg_out / neg_norms");
+  MHR_REQUIRE((!row_of && !src_of) || (row_of && src_of && capacity > 0 && n_item_ids > 0),
+              "embedding_gather_step: a packed x_out needs row_of, src_of and its capacity (%d)", capacity);
   if (n_ids == 0) return MHR_OK;
   const int grid_items = n_item_ids ? mhr_grid_for(n_item_ids, 16) : 0;
   const int grid_negs = n_ids > n_item_ids ? mhr_grid_for(n_ids - n_item_ids, 8) : 0;
   hipStream_t s = (hipStream_t)stream;
 #define LG(NC)                                                                                                              \
   hipLaunchKernelGGL((gather_step_kernel<NC>), dim3(grid_items + grid_negs), dim3(256), 0, s, table, n_rows, dim, ids, n_ids, \
-                     n_item_ids, rows_out, pos_table, seq_len, window_len, x_out, (bf16_t*)neg_out, neg_norms, grid_items)
+                     n_item_ids, rows_out, pos_table, seq_len, window_len, x_out, (bf16_t*)neg_out, neg_norms, grid_items,  \
+                     row_of, src_of, capacity)
   const int nc = (dim + 255) / 256;
   if (nc <= 1) LG(1);
   else if (nc <= 2) LG(2);
@@ -283,6 +299,7 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const int64_t* __restr
                                                           const AT* __restrict__ ga, int64_t n_a,
                                                           const BT* __restrict__ gb, int64_t n_b,
                                                           const float* __restrict__ xg, int seq_len, int window_len,
+                                                          const int32_t* __restrict__ x_row_of,
                                                           float* __restrict__ out_rows, int32_t* __restrict__ row_slot,
                                                           int64_t n_rows, int dim) {
   const int lane = threadIdx.x & 63;
@@ -325,8 +342,12 @@ __global__ __launch_bounds__(256) void segment_sum_kernel(const int64_t* __restr
                 const int64_t b = r / window_len;
                 const int l = (int)(r - b * window_len);
                 if (l < seq_len) {
-                  vx[u] = *reinterpret_cast<const f32x4*>(xg + (b * seq_len + l) * dim + c);
-                  use_x[u] = true;
+                  // (x_row_of: xg holds the PACKED rows of the valid positions; a padding position has none)
+                  const int64_t xr = x_row_of ? (int64_t)x_row_of[b * seq_len + l] : b * seq_len + l;
+                  if (xr >= 0) {
+                    vx[u] = *reinterpret_cast<const f32x4*>(xg + xr * dim + c);
+                    use_x[u] = true;
+                  }
                 }
               }
             } else if (r - n_a < n_b) {
@@ -431,21 +452,23 @@ __global__ __launch_bounds__(64 * FIX_WAVES) void segment_fixup_kernel(const int
 
 extern "C" int mhr_sparse_rows_segment_sum(const int64_t* sorted_ids, const int64_t* perm, int64_t n_ids,
                                            const void* grad_a, int a_dtype, int64_t n_a, const void* grad_b, int b_dtype,
-                                           int64_t n_b, const float* x_grad, int seq_len, int window_len, float* out_rows,
-                                           int32_t* row_slot, int64_t n_rows, int dim, void* stream) {
+                                           int64_t n_b, const float* x_grad, int seq_len, int window_len,
+                                           const int32_t* x_row_of, float* out_rows, int32_t* row_slot, int64_t n_rows, int dim,
+                                           void* stream) {
   MHR_REQUIRE(sorted_ids && perm && out_rows && row_slot, "sparse_rows_segment_sum: null pointer");
   MHR_REQUIRE(dim > 0 && dim % 4 == 0 && n_rows > 0, "sparse_rows_segment_sum: dim=%d must be a multiple of 4", dim);
   MHR_REQUIRE((n_a == 0 || grad_a) && (n_b == 0 || grad_b), "sparse_rows_segment_sum: null gradient buffer");
   MHR_REQUIRE(n_a + n_b >= n_ids, "sparse_rows_segment_sum: n_a+n_b < n_ids");
   if (x_grad) MHR_REQUIRE(window_len > 0 && seq_len > 0 && n_a % window_len == 0, "sparse_rows_segment_sum: bad window");
+  MHR_REQUIRE(!x_row_of || x_grad, "sparse_rows_segment_sum: x_row_of without x_grad");
   if (n_ids == 0) return MHR_OK;
   if (window_len <= 0) window_len = 1;
   hipStream_t s = (hipStream_t)stream;
   int grid = mhr_grid_for((n_ids + SEG_CHUNK - 1) / SEG_CHUNK, 4);
 #define LAUNCH(AT, BT)                                                                                               \
   hipLaunchKernelGGL((segment_sum_kernel<AT, BT>), dim3(grid), dim3(256), 0, s, sorted_ids, perm, n_ids,             \
-                     (const AT*)grad_a, n_a, (const BT*)grad_b, n_b, x_grad, seq_len, window_len, out_rows, row_slot, \
-                     n_rows, dim)
+                     (const AT*)grad_a, n_a, (const BT*)grad_b, n_b, x_grad, seq_len, window_len, x_row_of, out_rows, \
+                     row_slot, n_rows, dim)
   bool ab = a_dtype == MHR_BF16, bb = b_dtype == MHR_BF16;
   if (ab && bb) LAUNCH(bf16_t, bf16_t);
   else if (ab) LAUNCH(bf16_t, float);
@@ -458,6 +481,91 @@ extern "C" int mhr_sparse_rows_segment_sum(const int64_t* sorted_ids, const int6
     hipLaunchKernelGGL(segment_fixup_kernel, dim3(fgrid), dim3(64 * FIX_WAVES), 0, s, sorted_ids, n_ids, out_rows, dim);
     MHR_CHECK_LAUNCH("sparse_rows_segment_sum (fix-up)");
   }
+  return MHR_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the packed encoder input's gradient (d_x [capacity, dim]: the valid positions back to back, csrc/rows_pack.hip), read
+// through the batch's row_of map - no copy back to the [B, L, dim] windows
+// ------------------------------------------------------------------------------------------
+// Position-table gradient: out[l, :] += sum_b d_x[row_of[b L + l], :] (hstu.py:640-643's backward).  One workgroup per
+// (position, 256-column block); its POS_WAVES waves take contiguous ranges of b, eight rows in flight each, and the partial sums
+// are added in wave order: one fixed order per element, no atomics.
+constexpr int POS_WAVES = 8;
+__global__ __launch_bounds__(64 * POS_WAVES) void pos_grad_packed_kernel(const float* __restrict__ d_x,
+                                                                         const int32_t* __restrict__ row_of, int B, int L, int dim,
+                                                                         float* __restrict__ out) {
+  __shared__ f32x4 part[POS_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int l = blockIdx.x, c = blockIdx.y * 256 + lane * 4;
+  const bool col = c < dim;
+  const int per = (B + POS_WAVES - 1) / POS_WAVES;
+  const int b_lo = wave * per, b_hi = min(B, b_lo + per);
+  constexpr int U = 8;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int b0 = b_lo; b0 < b_hi; b0 += U) {
+    int r[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) r[u] = b0 + u < b_hi ? row_of[(int64_t)(b0 + u) * L + l] : -1;
+    f32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      v[u] = (r[u] >= 0 && col) ? *reinterpret_cast<const f32x4*>(d_x + (int64_t)r[u] * dim + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc += v[u];
+  }
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && col) {
+    f32x4 tot = *reinterpret_cast<const f32x4*>(out + (int64_t)l * dim + c);
+    for (int w = 0; w < POS_WAVES; ++w) tot += part[w][lane];
+    *reinterpret_cast<f32x4*>(out + (int64_t)l * dim + c) = tot;
+  }
+}
+
+extern "C" int mhr_pos_grad_packed(const float* d_x, const int32_t* row_of, int B, int L, int dim, float* out, void* stream) {
+  MHR_REQUIRE(d_x && row_of && out, "pos_grad_packed: null pointer");
+  MHR_REQUIRE(B > 0 && L > 0 && dim > 0 && dim % 4 == 0, "pos_grad_packed: bad sizes (B=%d L=%d dim=%d)", B, L, dim);
+  MHR_REQUIRE(((uintptr_t)d_x | (uintptr_t)out) % 16 == 0, "pos_grad_packed: buffers must be 16-byte aligned");
+  hipLaunchKernelGGL(pos_grad_packed_kernel, dim3(L, (dim + 255) / 256), dim3(64 * POS_WAVES), 0, (hipStream_t)stream, d_x, row_of, B, L,
+                     dim, out);
+  MHR_CHECK_LAUNCH("pos_grad_packed");
+  return MHR_OK;
+}
+
+// out[b W + l, :] = rows[b W + l, :] + (l < L and row_of[b L + l] >= 0 ? d_x[row_of[b L + l], :] : 0): the item windows' gradient
+// rows with the packed input-side gradient folded in, written to a buffer of the caller's own (data parallel / accumulating
+// steps, whose rows travel on to the cross-rank exchange).  One wave per row.
+__global__ __launch_bounds__(256) void window_rows_add_packed_kernel(const float* __restrict__ rows, int64_t n_rows, int window_len,
+                                                                     int seq_len, const float* __restrict__ d_x,
+                                                                     const int32_t* __restrict__ row_of, int dim,
+                                                                     float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t n_waves = (int64_t)gridDim.x * 4;
+  for (int64_t r = wave; r < n_rows; r += n_waves) {
+    const int64_t b = r / window_len;
+    const int l = (int)(r - b * window_len);
+    const int xr = l < seq_len ? row_of[b * seq_len + l] : -1;
+    for (int c = lane * 4; c < dim; c += 256) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(rows + r * dim + c);
+      if (xr >= 0) v += *reinterpret_cast<const f32x4*>(d_x + (int64_t)xr * dim + c);
+      *reinterpret_cast<f32x4*>(out + r * dim + c) = v;
+    }
+  }
+}
+
+extern "C" int mhr_window_rows_add_packed(const float* rows, int64_t n_rows, int window_len, int seq_len, const float* d_x,
+                                          const int32_t* row_of, int dim, float* out, void* stream) {
+  MHR_REQUIRE(rows && d_x && row_of && out, "window_rows_add_packed: null pointer");
+  MHR_REQUIRE(n_rows >= 0 && window_len > 0 && seq_len > 0 && seq_len <= window_len && n_rows % window_len == 0 && dim > 0 &&
+              dim % 4 == 0, "window_rows_add_packed: bad sizes (rows=%lld window=%d seq=%d dim=%d)", (long long)n_rows, window_len,
+              seq_len, dim);
+  MHR_REQUIRE(((uintptr_t)rows | (uintptr_t)d_x | (uintptr_t)out) % 16 == 0, "window_rows_add_packed: buffers must be 16-byte aligned");
+  if (n_rows == 0) return MHR_OK;
+  hipLaunchKernelGGL(window_rows_add_packed_kernel, dim3(mhr_grid_for(n_rows, 4)), dim3(256), 0, (hipStream_t)stream, rows, n_rows,
+                     window_len, seq_len, d_x, row_of, dim, out);
+  MHR_CHECK_LAUNCH("window_rows_add_packed");
   return MHR_OK;
 }
 

@@ -5,6 +5,10 @@
 // silu'(z) in bf16 (the operand of the weight / input gradient GEMMs), dx = sum_h d_out (the residual branch) in fp32.
 // Replaces F.silu + broadcast add + permute().contiguous() (3 passes over the 105 MB head tensor) and silu_backward + two
 // layout copies + a sum over heads in the backward.  One wave per token, 16 bytes per lane.
+// Packed rows (csrc/rows_pack.hip): the valid positions of a batch are ONE sequence of `capacity` rows - n_tok = seq_len =
+// capacity gives b = 0, l = t, so x / z are read as [capacity, .] and the head rows are [H, capacity, D], addressed by the token
+// lists of mhr_token_compact's packed form.  The zero rows behind the valid count give silu(bias) forward (finite, read by
+// nobody) and, with the zero gradient rows nobody writes, zeros backward.
 #include "mhr_common.h"
 
 namespace {

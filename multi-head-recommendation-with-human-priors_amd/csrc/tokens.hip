@@ -38,7 +38,9 @@ __global__ __launch_bounds__(256) void token_scatter_kernel(const uint8_t* __res
                                                             int n_slots, int n_chunks, int tok_cap,
                                                             const int32_t* __restrict__ chunk_cnt, int32_t* __restrict__ q_idx,
                                                             int32_t* __restrict__ p_idx, int32_t* __restrict__ o_idx,
-                                                            int32_t* __restrict__ n_tok, int32_t* __restrict__ tok_of_slot) {
+                                                            int32_t* __restrict__ n_tok, int32_t* __restrict__ tok_of_slot,
+                                                            const int32_t* __restrict__ row_of, int seq_len, int n_heads,
+                                                            int head_stride, unsigned int* __restrict__ bad) {
   const int chunk = blockIdx.x, grp = blockIdx.y;
   const uint8_t* m = mask + (int64_t)grp * n_slots;
   const int32_t* cc = chunk_cnt + grp * n_chunks;
@@ -94,7 +96,22 @@ __global__ __launch_bounds__(256) void token_scatter_kernel(const uint8_t* __res
     const int i = __ffs(bits) - 1;
     bits &= bits - 1;
     if (off < tok_cap) {
-      qd[off] = qa[base + i];
+      int q = qa[base + i];
+      if (row_of) {
+        // PACKED head rows [n_heads, head_stride, D]: the window table's (b H + h) L + l names the position, the batch's row_of
+        // map its packed row.  A live token sits on a valid position: one without a packed row is a bug of the caller's mask or
+        // capacity - counted (mhr_bad_id_count), its query row is the head's row 0
+        const int hl = n_heads * seq_len;
+        const int b = q / hl, rem = q - b * hl;
+        const int h = rem / seq_len, l = rem - h * seq_len;
+        int r = row_of[(int64_t)b * seq_len + l];
+        if (r < 0 || r >= head_stride) {
+          if (bad) atomicAdd(bad, 1u);
+          r = 0;
+        }
+        q = h * head_stride + r;
+      }
+      qd[off] = q;
       pd[off] = p_all[base + i];
       od[off] = o_all[base + i];
     }
@@ -331,14 +348,18 @@ extern "C" int mhr_nce_log_counters(const int32_t* n_valid, const int32_t* rank,
 
 extern "C" int mhr_token_compact(const uint8_t* mask, const int32_t* q_all, const int32_t* p_all, const int32_t* o_all,
                                  int n_groups, int n_slots, int tok_cap, int32_t* q_idx, int32_t* p_idx, int32_t* o_idx,
-                                 int32_t* n_tok, int32_t* scratch, int32_t* tok_of_slot, void* stream) {
+                                 int32_t* n_tok, int32_t* scratch, int32_t* tok_of_slot, const int32_t* row_of, int seq_len,
+                                 int n_heads, int head_stride, void* stream) {
   MHR_REQUIRE(mask && q_all && p_all && o_all && q_idx && p_idx && o_idx && n_tok && scratch, "token_compact: null pointer");
   MHR_REQUIRE(n_groups >= 1 && n_groups <= 65535 && n_slots > 0 && tok_cap > 0, "token_compact: bad sizes");
+  MHR_REQUIRE(!row_of || (seq_len > 0 && n_heads > 0 && head_stride > 0 && (int64_t)n_heads * head_stride < (1ll << 31)),
+              "token_compact: packed head rows need seq_len, n_heads, head_stride (%d, %d, %d)", seq_len, n_heads, head_stride);
   const int n_chunks = (n_slots + CHUNK - 1) / CHUNK;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(token_count_kernel, dim3(n_chunks, n_groups), dim3(256), 0, s, mask, n_slots, n_chunks, scratch);
   hipLaunchKernelGGL(token_scatter_kernel, dim3(n_chunks, n_groups), dim3(256), 0, s, mask, q_all, p_all, o_all, n_slots,
-                     n_chunks, tok_cap, scratch, q_idx, p_idx, o_idx, n_tok, tok_of_slot);
+                     n_chunks, tok_cap, scratch, q_idx, p_idx, o_idx, n_tok, tok_of_slot, row_of, seq_len, n_heads, head_stride,
+                     row_of ? mhr_bad_id_counter_addr() : nullptr);
   MHR_CHECK_LAUNCH("token_compact");
   return MHR_OK;
 }

@@ -135,14 +135,49 @@ def embedding_scatter_add(grad_rows, ids, grad_table):
     return grad_table
 
 
-def sparse_rows_segment_sum(sorted_ids, perm, grad_a, grad_b, x_grad, seq_len, window_len, out_rows, row_slot):
+def sparse_rows_segment_sum(sorted_ids, perm, grad_a, grad_b, x_grad, seq_len, window_len, out_rows, row_slot, x_row_of=None):
+    """x_row_of (int32 [B * seq_len], seq_pack_maps' row_of): x_grad is the PACKED [capacity, D] gradient of the encoder input."""
     D = out_rows.shape[-1]
+    if x_row_of is not None:
+        _chk(x_row_of, "x_row_of", torch.int32)
+        assert x_grad is not None and grad_a is not None and x_row_of.numel() == grad_a.numel() // D // window_len * seq_len
     n_a = 0 if grad_a is None else grad_a.numel() // D
     n_b = 0 if grad_b is None else grad_b.numel() // D
     _timed_call("mhr_sparse_rows_segment_sum", sorted_ids.data_ptr(), perm.data_ptr(), sorted_ids.numel(),
              _ptr(grad_a), _dt(grad_a) if grad_a is not None else F32, n_a,
              _ptr(grad_b), _dt(grad_b) if grad_b is not None else F32, n_b,
-             _ptr(x_grad), seq_len, window_len, out_rows.data_ptr(), row_slot.data_ptr(), row_slot.numel(), D, _stream())
+             _ptr(x_grad), seq_len, window_len, _ptr(x_row_of), out_rows.data_ptr(), row_slot.data_ptr(), row_slot.numel(), D,
+             _stream())
+
+
+def pos_grad_packed(d_x, row_of, B, L, out):
+    """out [>= L, D] fp32 += the position table's gradient from the PACKED encoder-input gradient d_x [capacity, D]:
+    out[l] += sum_b d_x[row_of[b L + l]] (mhr_pos_grad_packed; fixed order, no atomics)."""
+    _chk(d_x, "d_x", torch.float32)
+    _chk(row_of, "row_of", torch.int32)
+    _chk(out, "out", torch.float32)
+    D = d_x.shape[-1]
+    assert row_of.numel() == B * L and out.numel() >= L * D
+    lib.call("mhr_pos_grad_packed", d_x.data_ptr(), row_of.data_ptr(), int(B), int(L), D, out.data_ptr(), _stream())
+    return out
+
+
+def window_rows_add_packed(rows, window, L, d_x, row_of, out=None):
+    """The item windows' gradient rows [B * window, D] fp32 with the packed input-side gradient d_x [capacity, D] added at the
+    valid positions (row_of [B * L]), written to `out` (default: a new tensor); `rows` is left as it came."""
+    _chk(rows, "rows", torch.float32)
+    _chk(d_x, "d_x", torch.float32)
+    _chk(row_of, "row_of", torch.int32)
+    D = rows.shape[-1]
+    n = rows.numel() // D
+    assert n % window == 0 and row_of.numel() == n // window * L
+    if out is None:
+        out = torch.empty_like(rows)
+    _chk(out, "out", torch.float32)
+    assert out.shape == rows.shape
+    lib.call("mhr_window_rows_add_packed", rows.data_ptr(), n, int(window), int(L), d_x.data_ptr(), row_of.data_ptr(), D,
+             out.data_ptr(), _stream())
+    return out
 
 
 def adam_rows(w, m, v, grad_rows, row_slot, step, lr, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
@@ -339,9 +374,11 @@ def l2norm_rows_bwd(dy, x, norms):
     return dx
 
 
-def embedding_gather_step(table, pos_table, ids_all, n_item_ids, seq_len, window):
+def embedding_gather_step(table, pos_table, ids_all, n_item_ids, seq_len, window, pack=None):
     """One launch for a training step's table reads: item windows -> (rows fp32 [n_item_ids, D], x fp32 [B, seq_len, D] with the
-    position add); negative-pool ids -> (normalised bf16 rows [n_neg, D], norms fp32 [n_neg])."""
+    position add); negative-pool ids -> (normalised bf16 rows [n_neg, D], norms fp32 [n_neg]).
+    pack = (row_of, src_of, capacity) of seq_pack_maps: x is the PACKED encoder input [capacity, D] (valid positions back to back,
+    zero rows behind them) - what rows_gather_masked would make of the window form, bit for bit, without the window form."""
     _chk(table, "table", torch.float32)
     _chk(pos_table, "pos_table", torch.float32)
     _chk(ids_all, "ids_all", torch.int64)
@@ -350,11 +387,22 @@ def embedding_gather_step(table, pos_table, ids_all, n_item_ids, seq_len, window
     n = ids_all.numel()
     n_neg = n - n_item_ids
     rows = torch.empty(n_item_ids, D, dtype=torch.float32, device=dev)
-    x = torch.empty(n_item_ids // window, seq_len, D, dtype=torch.float32, device=dev)
+    row_of = src_of = None
+    cap = 0
+    if pack is not None:
+        row_of, src_of, cap = pack
+        _chk(row_of, "row_of", torch.int32)
+        _chk(src_of, "src_of", torch.int32)
+        cap = int(cap)
+        assert row_of.numel() == n_item_ids // window * seq_len and src_of.numel() == cap
+        x = torch.empty(cap, D, dtype=torch.float32, device=dev)
+    else:
+        x = torch.empty(n_item_ids // window, seq_len, D, dtype=torch.float32, device=dev)
     negs = torch.empty(n_neg, D, dtype=torch.bfloat16, device=dev)
     norms = torch.empty(n_neg, dtype=torch.float32, device=dev)
     _timed_call("mhr_embedding_gather_step", table.data_ptr(), table.shape[0], D, ids_all.data_ptr(), n, n_item_ids, rows.data_ptr(),
-                pos_table.data_ptr(), seq_len, window, x.data_ptr(), negs.data_ptr(), norms.data_ptr(), _stream())
+                pos_table.data_ptr(), seq_len, window, x.data_ptr(), negs.data_ptr(), norms.data_ptr(), _ptr(row_of), _ptr(src_of),
+                cap, _stream())
     return rows, x, negs, norms
 
 
@@ -423,6 +471,7 @@ def rows_gather_masked(src, idx, out=None):
 
 
 PACK_ROWS = os.environ.get("MHR_PACK_ROWS", "1") != "0"          # encoder over the valid rows only when the batch carries a row capacity
+PACK_HEADS = os.environ.get("MHR_PACK_HEADS", "1") != "0"        # ... and the embedding gather, the decoding heads and the loss with it: no window-shaped activation in a train step
 DEAD_ROWS = os.environ.get("MHR_DEAD_ROWS", "1") != "0"          # row-wise encoder kernels do not load rows in front of a sequence's first valid key
 SEQ_LAYOUT = os.environ.get("MHR_ATTN_SEQ_LAYOUT", "1") != "0"   # skip leading all-padding blocks + longest-sequences-first launch order
 
@@ -610,11 +659,13 @@ def softmax_attn_bwd(qkv, out, d_out, lse, n_seqs, max_len, n_heads, n_kv_heads,
 # ------------------------------------------------------------------------------------------------
 # sampled softmax
 # ------------------------------------------------------------------------------------------------
-def token_compact(mask, q_all, p_all, o_all, tok_cap=None, slot_map=False):
+def token_compact(mask, q_all, p_all, o_all, tok_cap=None, slot_map=False, packed=None):
     """Ordered compaction of live (group, slot) pairs.  mask [G, n_slots] bool/uint8; q_all [G, n_slots] int32;
     p_all, o_all [n_slots] int32.  Returns (q_idx, p_idx, o_idx [G, cap] int32 - entries beyond n_tok undefined -,
     n_tok [G] int32) with cap = tok_cap (default n_slots) rounded up to a multiple of 32.  No host sync.
-    slot_map: also return tok_of_slot [G, n_slots] int32 (list position of a live slot, -1 otherwise)."""
+    slot_map: also return tok_of_slot [G, n_slots] int32 (list position of a live slot, -1 otherwise).
+    packed = (row_of, seq_len, n_heads, head_stride): q_all holds the window form (b H + h) L + l and q_idx receives the PACKED
+    head row h * head_stride + row_of[b L + l] (head rows [H, head_stride, D] over seq_pack_maps' rows); everything else as before."""
     if mask.dtype == torch.bool:
         mask = mask.view(torch.uint8)
     _chk(mask, "mask", torch.uint8)
@@ -631,8 +682,12 @@ def token_compact(mask, q_all, p_all, o_all, tok_cap=None, slot_map=False):
     n_tok = torch.empty(G, dtype=torch.int32, device=dev)
     scratch = torch.empty(G, (n_slots + 4095) // 4096, dtype=torch.int32, device=dev)
     tos = torch.empty(G, n_slots, dtype=torch.int32, device=dev) if slot_map else None
+    row_of, seq_len, n_heads, head_stride = packed if packed is not None else (None, 0, 0, 0)
+    if row_of is not None:
+        _chk(row_of, "row_of", torch.int32)
     lib.call("mhr_token_compact", mask.data_ptr(), q_all.data_ptr(), p_all.data_ptr(), o_all.data_ptr(), G, n_slots, cap,
-             q_idx.data_ptr(), p_idx.data_ptr(), o_idx.data_ptr(), n_tok.data_ptr(), scratch.data_ptr(), _ptr(tos), _stream())
+             q_idx.data_ptr(), p_idx.data_ptr(), o_idx.data_ptr(), n_tok.data_ptr(), scratch.data_ptr(), _ptr(tos),
+             _ptr(row_of), int(seq_len), int(n_heads), int(head_stride), _stream())
     if slot_map:
         return q_idx, p_idx, o_idx, n_tok, tos
     return q_idx, p_idx, o_idx, n_tok
