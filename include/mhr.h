@@ -282,9 +282,16 @@ int mhr_hstu_attn_bwd_seq(const void* q_pre, const void* k_pre, const void* v_pr
  * (window row b L + l of a packed row, -1 behind the last sequence), row_of [B L] (packed row of a window position, -1 for
  * padding).  capacity is the caller's static bound (a bucketed count known to the loader); positions past it are dropped and
  * overflow[0] (optional) receives the real count, 0 otherwise.  mhr_rows_gather_masked: out[r] = idx[r] >= 0 ? src[idx[r]] : 0
- * (f32 or bf16 rows) - pack, unpack and both their backward passes (the map is injective). */
+ * (f32 or bf16 rows) - pack, unpack and both their backward passes (the map is injective).
+ * mhr_seq_pack_maps_guarded: the same three launches and the same outputs, plus a STICKY overflow record in guard [4] int32 -
+ * persistent words of the caller, zeroed once, that no launch clears: when the batch's valid count exceeds the capacity,
+ * guard[0] += 1 (overflowing calls), guard[1] = max(guard[1], count), guard[2] = the capacity of the call that set guard[1];
+ * guard[3] is reserved (stays 0).  A fitting batch leaves the words untouched, so they survive any number of graph replays
+ * until the host reads them. */
 int mhr_seq_pack_maps(const uint8_t* key_valid, int B, int L, int capacity, int32_t* cu_rows, int32_t* src_of, int32_t* row_of,
                       int32_t* overflow, void* stream);
+int mhr_seq_pack_maps_guarded(const uint8_t* key_valid, int B, int L, int capacity, int32_t* cu_rows, int32_t* src_of,
+                              int32_t* row_of, int32_t* overflow, int32_t* guard, void* stream);
 int mhr_rows_gather_masked(const void* src, int dtype, const int32_t* idx, void* out, int64_t n_out, int dim, void* stream);
 
 /* ------------------------------------------------------------------------------------------

@@ -27,12 +27,43 @@ Same distributions as the reference:
     negative pools exist for 'item' only (trainset.py:33);
   * weighted negatives (`neg_sample_mode`, trainset.py:99-107): draws WITH replacement from the pool with the weight list
     the reference hands to `random.choices(..., weights=...)`, items of the window rejected, repeats allowed.
+Packed encoder rows (`packed_rows`, config key, default off): the batchers know every window's valid length on the HOST
+(`loc` / `train_len`), so they hand each batch a static row capacity (`mhr_amd.synth.rows_capacity` of its valid context
+positions) without reading a device tensor: as `rows_cap` on the batch (a `Batch`: a tuple with that one attribute) and as
+`_mhr_rows_cap` on the mask / item_seq, the channel `HSTU` and the Trainer's step graphs read.  Data-parallel training: every
+rank computes the counts of ALL ranks' slices of the step from the shared permutation and takes the maximum - the same
+capacity on every rank in every step, with no collective.
 Out of scope here (data layer): parquet loading, id remapping, timestamps (`time_seq` is returned empty), building the
 weight lists from interaction counts (dataload.py:263-327) and the user clustering.
 """
 import math
 
 import torch
+
+
+class Batch(tuple):
+    """A train 4-tuple / eval 8-tuple (len, indexing and unpacking as before) carrying `rows_cap`: the static capacity of the
+    batch's valid context positions for the packed encoder rows, an int - or None when `packed_rows` is off."""
+    rows_cap = None
+
+    def __new__(cls, fields, rows_cap=None):
+        self = super().__new__(cls, fields)
+        self.rows_cap = None if rows_cap is None else int(rows_cap)
+        return self
+
+
+def _rows_capacity(n_valid, n_rows, bucket):
+    from mhr_amd.synth import rows_capacity
+    return rows_capacity(int(n_valid), n_rows=n_rows, bucket=bucket)
+
+
+def batch_rows_cap(mask_or_item_seq, L, bucket=None):
+    """Row capacity of a batch collated on the CPU: from the train mask [B, >= L] (its first L columns) or the eval item_seq
+    [B, L] (non-zero ids).  None for a tensor that is not on the CPU: counting there would cost a host sync per batch."""
+    t = mask_or_item_seq
+    if not torch.is_tensor(t) or t.device.type != "cpu" or t.dim() != 2:
+        return None
+    return _rows_capacity(int((t[:, :L] != 0).sum()), t.shape[0] * L, bucket)
 
 
 class SeqStore:
@@ -156,7 +187,7 @@ def _draw_weighted(pool, weights, n_draw, black, gen):
 class SeqTrainBatcher:
     """Iterable over train batches for one rank (reference SEQTrainDataset + DistributedSampler + default collate)."""
 
-    def __init__(self, config, store, batch_size=None, rank=0, world=1, seed=2020):
+    def __init__(self, config, store, batch_size=None, rank=0, world=1, seed=2020, rows_bucket=None):
         self.store, self.rank, self.world = store, rank, world
         self.L, self.P = config['MAX_ITEM_LIST_LENGTH'], config['pred_len']
         self.B = batch_size or config['train_batch_size']
@@ -186,12 +217,15 @@ class SeqTrainBatcher:
         self.gen.manual_seed(seed + 1000003 * (rank + 1))
         self.perm_gen = torch.Generator()                              # shared by all ranks: same permutation per epoch
         self.seed, self.epoch = seed, 0
+        # packed encoder rows: the context length of every sample location, min(context_end, L) (= mask[:, :L].sum(1)), on the host
+        self.packed_rows, self.rows_bucket = bool(config.get('packed_rows')), rows_bucket
+        self.ctx_len_host = self.loc[:, 1].clamp(max=self.L).cpu() if self.packed_rows else None
 
     def __len__(self):
         return math.ceil(math.ceil(self.loc.shape[0] / self.world) / self.B)
 
-    def batch(self, idx):
-        """idx [B] rows of the sample-location table -> the 4-tuple."""
+    def batch(self, idx, rows_cap=None):
+        """idx [B] rows of the sample-location table -> the 4-tuple (rows_cap: the batch's row capacity, see `__iter__`)."""
         st, L, P, dev = self.store, self.L, self.P, self.store.device
         W = L + P
         uid, end = self.loc[idx, 0], self.loc[idx, 1]
@@ -232,7 +266,20 @@ class SeqTrainBatcher:
         else:                                                   # the interaction's event type; zeros on the pads
             ev = st.events[src.clamp(0, st.events.numel() - 1)]
             tags = torch.nn.functional.one_hot(ev.clamp(0, self.n_cats - 1), self.n_cats) * real[..., None].long()
-        return items, neg_items, real.long(), tags
+        mask = real.long()
+        if rows_cap is not None:
+            mask._mhr_rows_cap = int(rows_cap)
+        return Batch((items, neg_items, mask, tags), rows_cap)
+
+    def _step_caps(self, perm_all, per_rank):
+        """Row capacity of every step of the epoch, the same on all ranks: perm_all (CPU, padded) viewed as [per_rank, world]
+        holds rank r's samples in column r, so the valid count of every rank's slice of every step is a sum over host lengths."""
+        B, W = self.B, self.world
+        steps = math.ceil(per_rank / B)
+        cnt = torch.zeros(steps * B, W, dtype=torch.int64)
+        cnt[:per_rank] = self.ctx_len_host[perm_all].view(per_rank, W)
+        worst = cnt.view(steps, B, W).sum(1).max(1).values.tolist()
+        return [_rows_capacity(worst[s_], min(B, per_rank - s_ * B) * self.L, self.rows_bucket) for s_ in range(steps)]
 
     def __iter__(self):
         n = self.loc.shape[0]
@@ -240,15 +287,17 @@ class SeqTrainBatcher:
         self.epoch += 1
         perm = torch.randperm(n, generator=self.perm_gen)
         total = math.ceil(n / self.world) * self.world
-        perm = torch.cat([perm, perm[:total - n]])[self.rank::self.world].to(self.store.device)   # DistributedSampler padding
+        perm_all = torch.cat([perm, perm[:total - n]])                                          # DistributedSampler padding
+        caps = self._step_caps(perm_all, total // self.world) if self.packed_rows else None
+        perm = perm_all[self.rank::self.world].to(self.store.device)
         for i0 in range(0, perm.numel(), self.B):
-            yield self.batch(perm[i0:i0 + self.B])
+            yield self.batch(perm[i0:i0 + self.B], None if caps is None else caps[i0 // self.B])
 
 
 class SeqEvalBatcher:
     """Iterable over eval batches for one rank (reference SeqEvalDataset + seq_eval_collate + rank-strided sampler)."""
 
-    def __init__(self, config, store, phase='valid', batch_size=None, rank=0, world=1):
+    def __init__(self, config, store, phase='valid', batch_size=None, rank=0, world=1, rows_bucket=None):
         self.store, self.phase = store, phase
         self.L = config['MAX_ITEM_LIST_LENGTH_TEST'] or config['MAX_ITEM_LIST_LENGTH']
         self.E = config['eval_pred_len']
@@ -267,11 +316,18 @@ class SeqEvalBatcher:
         self.users = torch.arange(1 + rank, store.user_num, world, device=store.device)
         self.num_total_examples = store.user_num - 1
         self.item_tags = store.item_tags
+        # packed encoder rows: min(n_hist, L) of this rank's users on the host (eval steps issue no collective: per rank;
+        # they are host-issued, so no graph per capacity and fine buckets)
+        self.packed_rows, self.rows_bucket = bool(config.get('packed_rows')), rows_bucket or 256
+        self.ctx_len_host = None
+        if self.packed_rows:
+            n_hist = store.train_len if phase == 'valid' else store.lens - self.E
+            self.ctx_len_host = n_hist[self.users].clamp(0, self.L).cpu()
 
     def __len__(self):
         return math.ceil(self.users.numel() / self.B)
 
-    def batch(self, uid):
+    def batch(self, uid, rows_cap=None):
         st, L, E, dev = self.store, self.L, self.E, self.store.device
         B = uid.numel()
         n_hist = st.train_len[uid] if self.phase == 'valid' else st.lens[uid] - E
@@ -313,8 +369,13 @@ class SeqEvalBatcher:
             cnt = torch.zeros(B, st.item_tags.shape[1], dtype=torch.int32, device=dev)
             cnt.index_add_(0, hu, fixed(st.item_tags[hi]).int())
             outlier = (fixed(st.item_tags[item_target]) & ~(cnt > 0)[:, None, :]).any(-1).any(-1)
-        return uid, item_seq, item_target, (hu, hi), positive_u, torch.zeros(B, 0, device=dev), tt, outlier
+        if rows_cap is not None:
+            item_seq._mhr_rows_cap = int(rows_cap)
+        return Batch((uid, item_seq, item_target, (hu, hi), positive_u, torch.zeros(B, 0, device=dev), tt, outlier), rows_cap)
 
     def __iter__(self):
         for i0 in range(0, self.users.numel(), self.B):
-            yield self.batch(self.users[i0:i0 + self.B])
+            uid, cap = self.users[i0:i0 + self.B], None
+            if self.packed_rows:
+                cap = _rows_capacity(int(self.ctx_len_host[i0:i0 + self.B].sum()), uid.numel() * self.L, self.rows_bucket)
+            yield self.batch(uid, cap)

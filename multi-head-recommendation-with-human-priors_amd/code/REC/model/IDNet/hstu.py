@@ -116,6 +116,9 @@ class HSTU(MultiHeadDecoding, BaseModel):
         self._init_multihead(config, dataload, D, temp_init=1 / 0.05)
 
         self.register_buffer("_attn_mask", torch.triu(torch.ones((L, L), dtype=torch.bool), diagonal=1))
+        # sticky overflow record of the packed encoder rows (mhr_seq_pack_maps_guarded; read by `check_pack_guard`): made here,
+        # outside any capture, so that a replayed step writes the words the host later reads; not part of the state_dict
+        self.register_buffer("_pack_guard", torch.zeros(4, dtype=torch.int32), persistent=False)
         self._verbose = False
         self.reset_params()
 
@@ -208,7 +211,8 @@ class HSTU(MultiHeadDecoding, BaseModel):
         (csrc/rows_pack.hip), the attention addresses the sequences through cu_rows.  Same condition as the dead rows: nothing
         may read the hidden states of padding positions.  Data parallel: the capacity is part of the batch signature the step
         graphs are keyed on, and every rank must capture and replay in the same steps (a capture issues no collective) - the
-        loaders must hand all ranks the SAME capacity for a step (the maximum over the ranks; bench.py does that).
+        loaders must hand all ranks the SAME capacity for a step (the maximum over the ranks; bench.py and, with `packed_rows`,
+        REC/data/batcher.py do that).
         The maps depend on the mask only: `forward` builds them in front of the embedding gather and the early loss stages."""
         from mhr_amd import ops
         n = len(self._hstu._attention_layers)
@@ -220,9 +224,10 @@ class HSTU(MultiHeadDecoding, BaseModel):
                 and D % 8 == 0 and self._packable(L)):
             return None
         cap = int(cap)
-        cu, src_of, row_of, overflow = ops.seq_pack_maps(key_valid, B, L, cap)
+        cu, src_of, row_of, overflow = ops.seq_pack_maps(key_valid, B, L, cap, guard=self._pack_guard)
         # a capacity below the batch's valid positions would silently drop rows: the first host-issued steps at a capacity
-        # read the count back (a captured step cannot, and later steps trust the loader)
+        # read the count back; a captured step cannot, and later steps leave the overflow in `_pack_guard` for
+        # `check_pack_guard` (the Trainer calls it where it reads the loss anyway)
         seen = self.__dict__.setdefault("_pack_checked", {})
         if not torch.cuda.is_current_stream_capturing() and seen.get(cap, 0) < 4:
             seen[cap] = seen.get(cap, 0) + 1
@@ -230,6 +235,21 @@ class HSTU(MultiHeadDecoding, BaseModel):
                 raise RuntimeError(f"packed encoder rows: the batch has {int(overflow.item())} valid positions, "
                                    f"its capacity hint (_mhr_rows_cap) says {cap}")
         return cap, cu, src_of, row_of
+
+    def check_pack_guard(self):
+        """Has a batch on packed rows held more valid positions than its capacity hint since the last call?  Reads the four
+        guard words (ONE host sync); raises RuntimeError - and clears the record - if so, else returns None.  Such a batch
+        lost its last rows: the steps since the last check trained on truncated sequences."""
+        g = self._pack_guard
+        if not g.is_cuda:
+            return None
+        n_over, n_max, cap, _ = g.tolist()
+        if n_over == 0:
+            return None
+        g.zero_()
+        raise RuntimeError(f"packed encoder rows: {n_over} batch(es) held more valid positions than their capacity hint "
+                           f"(_mhr_rows_cap); the largest had {n_max} valid positions for a capacity of {cap} - the rows past "
+                           f"the capacity were dropped")
 
     def _encode(self, x, key_valid, training=None, want_bf16=False, plan=None):
         """x [B,L,D] fp32, key_valid [B,L] uint8 -> [B,L,D] fp32 (reference hstu.py:221-328); want_bf16: (out, its bf16 copy -

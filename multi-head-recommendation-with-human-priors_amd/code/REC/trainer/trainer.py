@@ -345,10 +345,30 @@ class Trainer(object):
         warm = self.total_iters * self.scheduler_config.get("warmup", 0.001)
         return base * cosine_warmup_factor(step, warm, self.total_iters)
 
+    def _rows_hint(self, batch, t, L, bucket=None):
+        """The static row capacity of a batch for the packed encoder rows (`packed_rows`), read BEFORE the device copy (a Python
+        attribute does not survive `.to()`): the loader's own `rows_cap` (REC/data/batcher.py) - else, for a batch collated on the
+        CPU, counted from the mask / item_seq `t` there (`batch_rows_cap`; never on a device tensor: that would be a sync per
+        step).  Data parallel: all ranks must carry the SAME capacity in a step, which only the loader can arrange, so a batch
+        without a loader-provided `rows_cap` is not packed."""
+        cap = getattr(batch, "rows_cap", None)
+        if cap is None and self.config.get("packed_rows", False) and torch.is_tensor(t) and not _dp_active():
+            from REC.data.batcher import batch_rows_cap
+            cap = batch_rows_cap(t, L, bucket)
+        return cap
+
+    def _check_pack_guard(self):
+        """Raise if a packed batch overflowed its row capacity since the last check (HSTU.check_pack_guard: one small read)."""
+        m = self.model.module if hasattr(self.model, "module") else self.model
+        check = getattr(m, "check_pack_guard", None)
+        if check is not None:
+            check()
+
     def _check_nan(self, loss):
         if torch.isnan(loss):
             raise ValueError('Training loss is nan')
         if loss.is_cuda:                       # (the loss was just read: the device is idle, one more word costs nothing)
+            self._check_pack_guard()           # (first: rows dropped by a wrong capacity hint name the cause)
             from mhr_amd import ops
             bad = ops.bad_id_count()
             if bad:
@@ -431,7 +451,10 @@ class Trainer(object):
             if isinstance(data, dict):                                         # HLLM batches are dicts (hllm.py:482-493)
                 data = {k: (v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in data.items()}
             else:
+                cap = self._rows_hint(data, data[2] if len(data) > 2 else None, self.config["MAX_ITEM_LIST_LENGTH"])
                 data = tuple(d.to(self.device, non_blocking=True) for d in data)
+                if cap is not None:                                            # the channel the model and the step graphs read
+                    data[2]._mhr_rows_cap = int(cap)
             out = self.train_step_fn(data)
             running = out
             if self._micro_step % self.accumulate_grad:
@@ -458,6 +481,7 @@ class Trainer(object):
                 self.model.train()
                 if stop:
                     break
+        self._check_pack_guard()
         return self.best_valid_score, self.best_valid_result
 
     def _save_checkpoint(self):
@@ -541,7 +565,10 @@ class Trainer(object):
         next batch - consume it (the Collector does) or clone it.  graph=False forces the launch-by-launch form."""
         _, item_seq, item_target, history_index, positive_u, time_seq, target_tags, outlier_users = batched_data
         dev = self.device
+        cap = self._rows_hint(batched_data, item_seq, item_seq.shape[1], bucket=256)   # (host-issued steps: fine buckets)
         item_seq, item_target, target_tags = item_seq.to(dev), item_target.to(dev), target_tags.to(dev)
+        if cap is not None:
+            item_seq._mhr_rows_cap = int(cap)
         hist = history_index if self.config.get("suppress_history", True) else None
         k = max(self.config["topk"])
         if stats is None and graph is not False and hist is not None and self._eval_graph_ok(item_seq):
@@ -615,5 +642,6 @@ class Trainer(object):
             else:
                 summary[name][k] = round(vec[i] / max(1, total), dp)
                 i += 1
+        self._check_pack_guard()
         self.model.train()
         return summary

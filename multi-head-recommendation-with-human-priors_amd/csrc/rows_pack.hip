@@ -25,8 +25,11 @@ __global__ __launch_bounds__(64) void seq_len_kernel(const uint8_t* __restrict__
 }
 
 // in place: cu_rows[1 .. B] hold the lengths -> cu_rows[b] = number of valid positions in sequences 0 .. b-1, clamped to the capacity
-// (one workgroup; B <= 65536: a thread owns B / 256 consecutive sequences)
-__global__ __launch_bounds__(256) void seq_cu_kernel(int B, int cap, int32_t* __restrict__ cu_rows, int32_t* __restrict__ overflow) {
+// (one workgroup; B <= 65536: a thread owns B / 256 consecutive sequences).  guard (may be null; a compile-time null in
+// seq_cu_kernel): 4 persistent words of the caller that no launch ever clears - (overflowing calls, largest count seen, the
+// capacity of the call that set it, reserved) - so that an overflow inside a replayed graph is still there when the host looks.
+__device__ __forceinline__ void seq_cu_body(int B, int cap, int32_t* __restrict__ cu_rows, int32_t* __restrict__ overflow,
+                                            int32_t* __restrict__ guard) {
   __shared__ int s_part[256];
   const int t = threadIdx.x;
   const int per = (B + 255) / 256;
@@ -43,6 +46,10 @@ __global__ __launch_bounds__(256) void seq_cu_kernel(int B, int cap, int32_t* __
       run += c;
     }
     if (overflow) overflow[0] = run > cap ? run : 0;      // the batch does not fit the capacity: the rows past it are DROPPED
+    if (guard && run > cap) {                             // (a fitting batch touches nothing)
+      atomicAdd(&guard[0], 1);
+      if (atomicMax(&guard[1], run) < run) guard[2] = cap;
+    }
   }
   __syncthreads();
   int run = s_part[t];
@@ -52,6 +59,15 @@ __global__ __launch_bounds__(256) void seq_cu_kernel(int B, int cap, int32_t* __
     cu_rows[b + 1] = min(run, cap);
   }
   if (t == 0) cu_rows[0] = 0;
+}
+
+__global__ __launch_bounds__(256) void seq_cu_kernel(int B, int cap, int32_t* __restrict__ cu_rows, int32_t* __restrict__ overflow) {
+  seq_cu_body(B, cap, cu_rows, overflow, nullptr);
+}
+
+__global__ __launch_bounds__(256) void seq_cu_guarded_kernel(int B, int cap, int32_t* __restrict__ cu_rows,
+                                                             int32_t* __restrict__ overflow, int32_t* __restrict__ guard) {
+  seq_cu_body(B, cap, cu_rows, overflow, guard);
 }
 
 // one wave per sequence: row_of[(b, l)] = packed row of a valid position (-1: padding / past the capacity), src_of[packed] = b L + l;
@@ -119,6 +135,18 @@ extern "C" int mhr_seq_pack_maps(const uint8_t* key_valid, int B, int L, int cap
   hipLaunchKernelGGL(seq_cu_kernel, dim3(1), dim3(256), 0, s, B, capacity, cu_rows, overflow);
   hipLaunchKernelGGL(seq_maps_kernel, dim3(B + 16), dim3(64), 0, s, key_valid, B, L, capacity, cu_rows, src_of, row_of);
   MHR_CHECK_LAUNCH("seq_pack_maps");
+  return MHR_OK;
+}
+
+extern "C" int mhr_seq_pack_maps_guarded(const uint8_t* key_valid, int B, int L, int capacity, int32_t* cu_rows, int32_t* src_of,
+                                         int32_t* row_of, int32_t* overflow, int32_t* guard, void* stream) {
+  MHR_REQUIRE(key_valid && cu_rows && src_of && row_of && guard, "seq_pack_maps_guarded: null pointer");
+  MHR_REQUIRE(B > 0 && B <= 65536 && L > 0 && capacity > 0 && (int64_t)B * L < (1ll << 31), "seq_pack_maps_guarded: bad sizes");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(seq_len_kernel, dim3(B), dim3(64), 0, s, key_valid, L, cu_rows);
+  hipLaunchKernelGGL(seq_cu_guarded_kernel, dim3(1), dim3(256), 0, s, B, capacity, cu_rows, overflow, guard);
+  hipLaunchKernelGGL(seq_maps_kernel, dim3(B + 16), dim3(64), 0, s, key_valid, B, L, capacity, cu_rows, src_of, row_of);
+  MHR_CHECK_LAUNCH("seq_pack_maps_guarded");
   return MHR_OK;
 }
 

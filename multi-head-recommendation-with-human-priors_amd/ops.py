@@ -446,16 +446,25 @@ def rows_gemm(a, w, bias=None, out=None, w_is_kn=False):
     return out
 
 
-def seq_pack_maps(key_valid, B, L, capacity):
-    """(cu_rows [B+1], src_of [capacity], row_of [B*L], overflow [1]) int32 of a batch of masks (mhr_seq_pack_maps)."""
+def seq_pack_maps(key_valid, B, L, capacity, guard=None):
+    """(cu_rows [B+1], src_of [capacity], row_of [B*L], overflow [1]) int32 of a batch of masks (mhr_seq_pack_maps).
+    guard (int32 [4] device tensor of the caller, zeroed once): the same maps through mhr_seq_pack_maps_guarded, which also
+    records an overflow in those words - (overflowing calls, largest count, its capacity, 0) - and never clears them."""
     _chk(key_valid, "key_valid", torch.uint8)
     dev = key_valid.device
     cu = torch.empty(B + 1, dtype=torch.int32, device=dev)
     src_of = torch.empty(capacity, dtype=torch.int32, device=dev)
     row_of = torch.empty(B * L, dtype=torch.int32, device=dev)
     overflow = torch.empty(1, dtype=torch.int32, device=dev)
-    lib.call("mhr_seq_pack_maps", key_valid.data_ptr(), B, L, int(capacity), cu.data_ptr(), src_of.data_ptr(), row_of.data_ptr(),
-             overflow.data_ptr(), _stream())
+    if guard is None:
+        lib.call("mhr_seq_pack_maps", key_valid.data_ptr(), B, L, int(capacity), cu.data_ptr(), src_of.data_ptr(), row_of.data_ptr(),
+                 overflow.data_ptr(), _stream())
+    else:
+        _chk(guard, "guard", torch.int32)
+        if guard.numel() != 4 or guard.device != dev:
+            raise ValueError("seq_pack_maps: guard must be int32 [4] on the mask's device")
+        lib.call("mhr_seq_pack_maps_guarded", key_valid.data_ptr(), B, L, int(capacity), cu.data_ptr(), src_of.data_ptr(),
+                 row_of.data_ptr(), overflow.data_ptr(), guard.data_ptr(), _stream())
     return cu, src_of, row_of, overflow
 
 
