@@ -416,18 +416,20 @@ int mhr_loss_reduce_bwd(const float* d_total, const float* bucket_cnt, const flo
  *   loss[t] = logsumexp(logits) - logit_pos;  lse[t] saved for backward (both written by mhr_nce_finalize).
  * Optional logs (may be NULL): n_valid[t] = 1 + #kept negatives; rank[t] = #kept negatives with logit > logit_pos
  * (hstu.py:621-629: nce_samples and top-k accuracy follow from these).
- * Saved for backward (may be NULL when no backward follows): qn_out/pn_out [tok_cap, dim] bf16 normalised rows,
+ * Saved for backward: qn_out/pn_out [tok_cap, dim] bf16 normalised rows,
  * supp_out [ceil(n_neg/32), tok_cap] uint32 (bit j of word [t, tok] = negative 32t+j suppressed for that token),
  * q_inv/p_inv [tok_cap] = 1/||row||, s_pos [tok_cap] = cos(q,p).
- * fix_words (optional, with u_out): scratch [n_groups, ceil(n_neg/32), round_up(n_p_rows, 256)] uint32, n_p_rows = rows of
- * p_rows.  The false-negative test cos(p, neg) > thres depends on the TARGET ROW only, and a row is the positive of many
- * tokens (every (position, offset) pair that points at it): with fix_words the test runs once per (group, row, negative)
- * into this bit table (a second launch, in front) and the fused forward carries the query operand only.  Same results.
+ * The forward is always the fused one: u_out is required (below), as are qn_out, q_inv, p_inv and tok_cap % 32 == 0.
+ * mhr_nce_fwd takes exactly two forms; any other combination of NULL pointers returns MHR_EINVAL before any launch.
+ * Hoisted form (fix_words, supp_out, pn_out set): fix_words is scratch [n_groups, ceil(n_neg/32), round_up(n_p_rows, 256)]
+ * uint32, n_p_rows = rows of p_rows.  The false-negative test cos(p, neg) > thres depends on the TARGET ROW only, and a row
+ * is the positive of many tokens (every (position, offset) pair that points at it): the test runs once per (group, row,
+ * negative) into this bit table (a second launch, in front) and the fused forward carries the query operand only.
  * fix_row_list [n_groups, round_up(n_p_rows, 256)] int32 + fix_n_rows [n_groups] int32 (device) + fix_slot_of_row
  * [n_groups, n_p_rows] int32 scratch (optional, together): the rows of p_rows that tokens of each group can point at
  * (any superset); only those are tested, column j of the bit table = list entry j, and the inverse map is written to
  * fix_slot_of_row.  Rows outside the list must not be referenced by live tokens of that group.
- * Plain form (u_out set; supp_out, fix_words and the fix_* lists NULL; pn_out optional; n_neg % 32 == 0): the fused
+ * Plain form (supp_out, fix_words and the fix_* lists NULL; pn_out optional; n_neg % 32 == 0): the fused
  * forward with NOTHING suppressed - no bit table, no suppression words loaded or stored, no bit test per logit.  This is
  * what the query-row-sharing path launches on its row list (the per-token kernels take the false negatives back out).
  * ---------------------------------------------------------------------------------------- */
@@ -439,15 +441,13 @@ int mhr_nce_fwd(const void* q_rows, const int32_t* q_idx, const void* p_rows, co
                 int log_group, float* u_out, int64_t n_p_rows, uint32_t* fix_words, const int32_t* fix_row_list,
                 const int32_t* fix_n_rows, int32_t* fix_slot_of_row, void* stream);
 /* log_group: the one group whose n_valid / rank are wanted (-1 = every group); the other groups skip the counting.
- * u_out (may be NULL; needs every saved tensor and tok_cap % 32 == 0): the TRAINING path.  [n_groups, tok_cap, dim] f32,
+ * u_out (required) [n_groups, tok_cap, dim] f32,
  *   u_out[g, t, :] = sum_j keep_tj exp(scale (s_tj - 1)) negs[g, j, :]
  * the unnormalised token-side gradient: d(loss_t)/d(qn_t) restricted to the negatives is exp(scale - lse_t) * scale *
  * u_out[t].  It is accumulated by the forward itself (the gated tile goes straight back into the matrix pipe against
  * the LDS-resident negatives), so the backward needs no second pass over the negatives for the token side. */
-/* The forward is split over negative ranges (grid.y) so that (token block, negative range) units fill the chip
- * without a tail: each unit adds its partial sum_j keep*exp(scale*(s_j - 1)) into sum_out[t] (and its counts into
- * n_valid / rank) with atomics - the caller zeroes sum_out, n_valid, rank - and mhr_nce_finalize produces
- * lse[t] = scale + log(sum[t] + exp(scale*(s_pos[t]-1))), loss[t] = lse[t] - scale*s_pos[t], n_valid[t] += 1. */
+/* sum_out[t] (and the counts n_valid / rank) are accumulated with atomics, so the caller zeroes them; mhr_nce_finalize
+ * produces lse[t] = scale + log(sum[t] + exp(scale*(s_pos[t]-1))), loss[t] = lse[t] - scale*s_pos[t], n_valid[t] += 1. */
 int mhr_nce_finalize(const float* sum, const float* s_pos, int n_groups, const int32_t* n_tok_dev, int tok_cap,
                      const float* logit_scale_dev, float* loss, float* lse, int32_t* n_valid,
                      const int32_t* bucket_idx, int n_buckets, float* bucket_sum, float* bucket_cnt, void* stream);

@@ -682,7 +682,7 @@ class NceLossFn(Function):
                 bucket_idx=None, n_buckets=0, log_group=-1, p_row_mask=None, share_rows=False, window=None, ihn_beta=0.0,
                 prep=None, bucket_weight=None, n_segments=1, exclusive_q_rows=False):
         sv = ops.nce_fwd(q_rows, q_idx, p_rows, p_idx, negs, n_tok_dev, tok_cap, logit_scale.detach().view(1), thres,
-                         want_logs=want_logs, for_backward=True, bucket_idx=bucket_idx, n_buckets=n_buckets,
+                         want_logs=want_logs, bucket_idx=bucket_idx, n_buckets=n_buckets,
                          log_group=log_group, p_row_mask=p_row_mask, share_rows=share_rows, window=window, ihn_beta=ihn_beta,
                          prep=prep)
         ctx.sv = sv

@@ -7,26 +7,32 @@
 //   s_ij = cos(q_i, n_j), f_ij = cos(p_i, n_j), s_i+ = cos(q_i, p_i), scale = exp(clamp(logit_scale, 0, ln 100))
 //   keep_ij = !(f_ij > thres);   lse_i = log( exp(scale*s_i+) + sum_j keep_ij exp(scale*s_ij) );   loss_i = lse_i - scale*s_i+
 //
-// Three kernels on the row-stationary streaming GEMM core (stream_gemm.h), all with S^T orientation
-// (streamed rows on accumulator registers, stationary rows on lanes).  One launch serves every prior category
-// (grid.z = group): per-group token lists (q_idx/p_idx into the shared head / target row matrices), per-group
-// negative pools, per-group live counts read from device memory (no host sync).
-//   nce_fwd    : tokens stationary (rows gathered through the index lists, L2-normalised in registers, kept as
-//                MFMA B fragments, 32 tokens per wave), 32-negative tiles streamed through a 3-slot LDS ring
-//                filled by LDS-DMA (global_load_lds_dwordx4); two MFMAs per LDS fragment read (s and f share
-//                the negative operand); running sums are one VGPR per lane because |logit| <= scale bounds the
-//                exponent (no running max).  Stores the normalised bf16 token rows, 1/||q||, 1/||p||, s+ and the
-//                false-negative suppression BITS (one bit per (token, negative)) for the backward.
-//   nce_finalize: per-token lse / loss / rank across the negative splits, per-group means.
-//   nce_bwd_q  : tokens stationary; recomputes s only (suppression comes from the saved bits);
-//                G_ij = w_i keep_ij exp(scale*s_ij - lse_i) in bf16 is the A operand of dQn += G . N, where the
-//                N^T fragments come from the SAME LDS tile via ds_read_b64_tr_b16 (no transposed copy).  The
-//                S(t) MFMAs carry the exp/convert epilogue of S(t-1) in their issue gaps (one-tile skew).
-//                Finishes with the L2-normalisation chain rule and adds dq/dp rows straight into the head /
-//                target row gradients with 256-B-shaped float atomics.
-//   nce_bwd_n  : negatives stationary (32 per wave), token tiles streamed (Qn tile + its w/lse/supp words by
-//                LDS-DMA); dN += G^T . Qn with Qn^T fragments from ds_read_b64_tr_b16; accumulated in registers
-//                across the workgroup's token share, then one float-atomic pass.
+// Kernels on the row-stationary streaming GEMM core (stream_gemm.h), all with S^T orientation (streamed rows on
+// accumulator registers, stationary rows on lanes).  One launch serves every prior category (grid.z = group): per-group
+// token lists (q_idx/p_idx into the shared head / target row matrices), per-group negative pools, per-group live counts
+// read from device memory (no host sync).
+//   nce_fix_bits : target rows stationary (64 per wave), negative tiles through a 3-slot LDS-DMA ring; one bit per
+//                  (group, target row, negative): cos(target, negative) > thres.  The filtered trio
+//                  (nce_neg_tile_norms, nce_fix_prefix, nce_fix_exact) writes the same table, rejecting almost every
+//                  (row fragment, tile) from a 64-column prefix and evaluating only the rest in full.
+//   nce_fwd_d    : the forward, fused with the token-side backward product.  Tokens stationary (rows gathered through
+//                  the index lists, L2-normalised in registers, kept as MFMA B fragments, 32 tokens per wave, one wave
+//                  per SIMD), 32-negative tiles through a 4-slot LDS-DMA ring (global_load_lds_dwordx4), hand-ordered
+//                  tile step sg::tile_step_pf: the s MFMAs of tile t carry the exp epilogue of tile t-1 in their gaps,
+//                  and the gated tile goes straight back into the matrix pipe for U = sum_j keep exp(scale (s - 1)) n_j.
+//                  Running sums are one VGPR per lane because |logit| <= scale bounds the exponent (no running max).
+//                  Stores the normalised bf16 token rows, 1/||q||, 1/||p||, s+ and U for the backward.
+//                  Hoisted form (SUPP = true): a token's suppression bits arrive as one word per tile from the bit table
+//                  and are saved per token for nce_bwd_n.  Plain form (SUPP = false): nothing is suppressed (the
+//                  row-sharing path, whose per-row kernels in nce_shared.hip take the false negatives back out).
+//   nce_finalize : per-token lse / loss from the sums, per-(group, offset) means.
+//   nce_bwd_rows : row-wise rest of the token-side backward: dQn_i = w_i exp(scale - lse_i) U_i, the positive-pair term,
+//                  the L2-normalisation chain rule, d(logit_scale); adds dq/dp rows straight into the head / target row
+//                  gradients with 256-B-shaped float atomics.
+//   nce_bwd_n    : negatives stationary (32 per wave), token tiles streamed (Qn tile + its lw / suppression words by
+//                  LDS-DMA) on the same 4-slot ring and tile step; dN += G^T . Qn with Qn^T fragments from
+//                  ds_read_b64_tr_b16; accumulated in registers across the workgroup's token share, then one
+//                  float-atomic pass.
 #include "mhr_common.h"
 #include "stream_gemm.h"
 
@@ -150,372 +156,6 @@ __device__ __forceinline__ float gate_dead(float s, float c1, float c0, uint32_t
   asm("v_exp_f32 %0, %2\n\tv_bfe_i32 %1, %3, %4, 1\n\tv_bfi_b32 %0, %1, 0, %0"                          // (m & 0) | (~m & e)
       : "=&v"(g), "=&v"(m) : "v"(x), "v"(dead_bits), "v"(pos));
   return g;
-}
-
-// ------------------------------------------------------------------------------------------
-// forward
-// ------------------------------------------------------------------------------------------
-template <int NKS, typename IT, bool LOGS>
-__global__ __launch_bounds__(256, 2) void nce_fwd_kernel(const IT* __restrict__ q_rows, const int32_t* q_idx,
-                                                         const IT* __restrict__ p_rows, const int32_t* p_idx,
-                                                         const bf16_t* negs, int n_neg,
-                                                         const int32_t* n_tok_dev, int tok_cap,
-                                                         const float* __restrict__ logit_scale_dev, float thres,
-                                                         int tiles_per_split, float* sum_out,
-                                                         int32_t* n_valid, int32_t* rank,
-                                                         bf16_t* qn_out, bf16_t* pn_out,
-                                                         uint32_t* supp_out, float* q_inv,
-                                                         float* p_inv, float* s_pos_out, int log_group) {
-  using T = sg::Tile<NKS>;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  // blockIdx.z selects the group (negative pool / prior category): every per-token array is [groups, tok_cap(, D)],
-  // negatives are [groups, n_neg, D]; query / positive source rows are shared.
-  {
-    const int64_t grp = blockIdx.z, to = grp * tok_cap;
-    q_idx += to; p_idx += to; n_tok_dev += grp; negs += grp * (int64_t)((n_neg + 31) & ~31) * T::DIM; sum_out += to;
-    if (n_valid) n_valid += to;
-    if (rank) rank += to;
-    if (qn_out) qn_out += to * T::DIM;
-    if (pn_out) pn_out += to * T::DIM;
-    if (supp_out) supp_out += grp * (int64_t)((n_neg + 31) >> 5) * tok_cap;
-    if (q_inv) q_inv += to;
-    if (p_inv) p_inv += to;
-    s_pos_out += to;
-  }
-  const int n_tok = min(*n_tok_dev, tok_cap);
-  const int tok0 = blockIdx.x * 128;
-  if (tok0 >= n_tok) return;
-  // blockIdx.y selects a contiguous range of negative tiles: (token block, negative range) units keep the
-  // 512 workgroup slots busy without a long tail; partial sums meet in sum_out (float atomics) and
-  // mhr_nce_finalize turns them into lse / loss.
-  const int n_tiles = (n_neg + 31) >> 5;
-  const int t_begin = blockIdx.y * tiles_per_split, t_end = min(n_tiles, t_begin + tiles_per_split);
-  if (t_begin >= t_end) return;
-  const bool first_split = blockIdx.y == 0;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, half = lane >> 5;
-  const int tok = tok0 + wave * 32 + r;
-  const bool live = tok < n_tok;
-
-  bf16x8 frag[2][NKS];   // [0] = normalised query, [1] = normalised positive
-  float qi = 0.f, pi = 0.f;
-  {
-    const IT* qs = q_rows + (live ? (int64_t)q_idx[tok] * T::DIM : 0);
-    const IT* ps = p_rows + (live ? (int64_t)p_idx[tok] * T::DIM : 0);
-    qi = row_inv_norm<NKS, IT>(qs, live, half);
-    pi = row_inv_norm<NKS, IT>(ps, live, half);
-    load_norm_frags<NKS, IT>(qs, live, half, qi, frag[0]);
-    load_norm_frags<NKS, IT>(ps, live, half, pi, frag[1]);
-  }
-  float spos = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) spos += (float)frag[0][ks][i] * (float)frag[1][ks][i];
-  spos += __shfl_xor(spos, 32, 64);
-  // Saved state for the backward.  Lanes past n_tok inside a processed block (tok < tok_cap) are written too - zero
-  // rows here and all-ones suppression words below - so that the backward can stream whole 32-token tiles without
-  // clamping: a padded token contributes exactly nothing.
-  const bool in_cap = tok < tok_cap;
-  if (in_cap && first_split) {
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const int k0 = ks * 16 + 8 * half;
-      if (qn_out) *reinterpret_cast<bf16x8*>(qn_out + (int64_t)tok * T::DIM + k0) = frag[0][ks];
-      if (pn_out) *reinterpret_cast<bf16x8*>(pn_out + (int64_t)tok * T::DIM + k0) = frag[1][ks];
-    }
-    if (live && half == 0) {
-      if (q_inv) q_inv[tok] = qi;
-      if (p_inv) p_inv[tok] = pi;
-      if (s_pos_out) s_pos_out[tok] = spos;
-    }
-  }
-
-  const float scale = clamp_scale(logit_scale_dev);
-  const float c1 = scale * LOG2E;
-  float sum = 0.f;
-  int nv = 0, rk = 0;
-
-  // Negative tiles stream through a 3-slot LDS-DMA ring (stream_gemm.h), branch-free: every iteration waits
-  // `vmcnt(PW)` (tile i landed, tile i+1 may be in flight) and issues the PW pieces of tile min(i+2, last) with
-  // SGPR-base addressing; the pool is padded to whole tiles, rows past n_neg are masked by `rem`.
-  using P = sg::DmaPieces<NKS>;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  P dp;
-  dp.init(wv, lane);
-  auto dma_tile = [&](auto slot_c, int tn) {
-    auto f = [&](auto k_c) {
-      dp.template piece<decltype(k_c)::value>(smem + decltype(slot_c)::value * T::BYTES,
-                                               reinterpret_cast<const char*>(negs) + (int64_t)tn * (32 * T::ROW_BYTES));
-    };
-    sg::static_for<P::PW>(f);
-  };
-  sg::LaneAddr<NKS> la;
-  la.init(lane);
-  const int n_loc = t_end - t_begin, t_last = t_end - 1;
-  const bool do_logs = LOGS && (log_group < 0 || (int)blockIdx.z == log_group);
-  dma_tile(std::integral_constant<int, 0>{}, t_begin);
-  dma_tile(std::integral_constant<int, 1>{}, min(t_begin + 1, t_last));
-  sg::ring_loop<3>(n_loc, [&](auto slot_c, int i) {
-    constexpr int cur = decltype(slot_c)::value, nxt = (cur + 2) % 3;
-    const int t = t_begin + i;
-    sg::wait_vmcnt<P::PW>();
-    sg::ring_barrier();
-    dma_tile(std::integral_constant<int, nxt>{}, min(t + 2, t_last));
-    f32x16 acc[2] = {sg::zero16(), sg::zero16()};
-    sg::mma_tile<NKS, 2>(smem + cur * T::BYTES, la, frag, acc);
-    const int rem = n_neg - t * 32;
-    // False negatives (cos(positive, negative) > thres) are rare: one max over the tile's 16 values per lane and a
-    // wave-wide vote select the common path, which is exp + add per logit and nothing else.
-    float fmax = acc[1][0];
-#pragma unroll
-    for (int g = 1; g < 16; g += 3) fmax = fmaxf(fmaxf(fmax, acc[1][g]), fmaxf(acc[1][g + 1], acc[1][g + 2]));
-    const bool plain = rem >= 32 && __builtin_amdgcn_ballot_w64(fmax > thres) == 0;
-    uint32_t sbits = 0;
-    if (plain) {
-#pragma unroll
-      for (int g = 0; g < 16; ++g) sum += fast_exp2(acc[0][g] * c1 - c1);
-      if (do_logs) {
-        nv += 16;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) rk += acc[0][g] > spos ? 1 : 0;
-      }
-    } else {
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const bool supp = acc[1][g] > thres;               // false negative: cos(positive, negative) > thres
-        const bool keep = (sg::crow(g, half) < rem) && !supp;
-        const float e = fast_exp2(acc[0][g] * c1 - c1);
-        sum += keep ? e : 0.f;
-        sbits |= supp ? (1u << sg::crow(g, half)) : 0u;
-        if (do_logs) {
-          nv += keep ? 1 : 0;
-          rk += (keep && acc[0][g] > spos) ? 1 : 0;
-        }
-      }
-      sbits |= __shfl_xor(sbits, 32, 64);
-    }
-    // one word per (negative tile, token): bit j = negative t*32+j suppressed
-    if (supp_out && in_cap && half == 0) supp_out[(int64_t)t * tok_cap + tok] = live ? sbits : 0xFFFFFFFFu;
-  });
-  sg::wait_vmcnt<0>();
-  sum += __shfl_xor(sum, 32, 64);
-  if (LOGS) {
-    nv += __shfl_xor(nv, 32, 64);
-    rk += __shfl_xor(rk, 32, 64);
-  }
-  if (live && half == 0) {
-    atomicAdd(sum_out + tok, sum);
-    if (LOGS) {
-      if (n_valid) atomicAdd(n_valid + tok, nv);
-      if (rank) atomicAdd(rank + tok, rk);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// forward fused with the token-side backward product (training path)
-// ------------------------------------------------------------------------------------------
-// dQn_i = sum_j G_ij n_j with G_ij = w_i keep_ij exp(scale s_ij - lse_i) factorises as
-//     dQn_i = w_i exp(scale - lse_i) * U_i,     U_i = sum_j keep_ij exp(scale (s_ij - 1)) n_j ,
-// and U_i needs neither lse nor w: it is the numerator that goes with the softmax denominator the forward already
-// accumulates (the flash-attention output accumulator without the running max - |logit| <= scale bounds the
-// exponent).  So the forward keeps a second accumulator U [32 tokens x D] per wave and feeds the gated tile
-// E = keep * exp(scale (s - 1)) (bf16, in registers) straight back into the matrix pipe against the SAME LDS tile
-// (transposed fragments).  The separate token-stationary backward kernel - a second full pass over the negatives
-// that recomputed every logit - disappears; what is left of it is a row-wise kernel (nce_bwd_rows_kernel below).
-// One wave per SIMD (U is 128 accumulator registers), 4-slot DMA ring, hand-ordered tile step (sg::tile_step, RF = 2):
-// the s and f MFMAs of tile t carry the exp / suppression epilogue of tile t-1 in their gaps.
-template <int NKS, typename IT, bool LOGS>
-__global__ __launch_bounds__(256, 1) void nce_fwd_u_kernel(const IT* __restrict__ q_rows, const int32_t* q_idx,
-                                                           const IT* __restrict__ p_rows, const int32_t* p_idx,
-                                                           const bf16_t* negs, int n_neg,
-                                                           const int32_t* n_tok_dev, int tok_cap,
-                                                           const float* __restrict__ logit_scale_dev, float thres,
-                                                           float* sum_out, int32_t* n_valid, int32_t* rank,
-                                                           bf16_t* qn_out, bf16_t* pn_out,
-                                                           uint32_t* supp_out, float* q_inv,
-                                                           float* p_inv, float* s_pos_out, int log_group,
-                                                           float* __restrict__ u_out) {
-  using T = sg::Tile<NKS>;
-  constexpr int ND = (NKS + 1) / 2;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  {
-    const int64_t grp = blockIdx.z, to = grp * tok_cap;
-    q_idx += to; p_idx += to; n_tok_dev += grp; negs += grp * (int64_t)((n_neg + 31) & ~31) * T::DIM; sum_out += to;
-    if (n_valid) n_valid += to;
-    if (rank) rank += to;
-    qn_out += to * T::DIM; pn_out += to * T::DIM; u_out += to * T::DIM;
-    supp_out += grp * (int64_t)((n_neg + 31) >> 5) * tok_cap;
-    q_inv += to; p_inv += to; s_pos_out += to;
-  }
-  const int n_tok = min(*n_tok_dev, tok_cap);
-  const int tok0 = blockIdx.x * 128;
-  if (tok0 >= n_tok) return;
-  const int n_tiles = (n_neg + 31) >> 5;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, half = lane >> 5;
-  const int tok = tok0 + wave * 32 + r;
-  const bool live = tok < n_tok;
-  const bool in_cap = tok < tok_cap;
-
-  bf16x8 frag[2][NKS];   // [0] = normalised query, [1] = normalised positive
-  float qi = 0.f, pi = 0.f;
-  {
-    const IT* qs = q_rows + (live ? (int64_t)q_idx[tok] * T::DIM : 0);
-    const IT* ps = p_rows + (live ? (int64_t)p_idx[tok] * T::DIM : 0);
-    qi = row_inv_norm<NKS, IT>(qs, live, half);
-    pi = row_inv_norm<NKS, IT>(ps, live, half);
-    load_norm_frags<NKS, IT>(qs, live, half, qi, frag[0]);
-    load_norm_frags<NKS, IT>(ps, live, half, pi, frag[1]);
-  }
-  float spos = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) spos += (float)frag[0][ks][i] * (float)frag[1][ks][i];
-  spos += __shfl_xor(spos, 32, 64);
-  // saved state; lanes past n_tok inside the block write zero rows / all-ones suppression words (see nce_fwd_kernel)
-  if (in_cap) {
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const int k0 = ks * 16 + 8 * half;
-      *reinterpret_cast<bf16x8*>(qn_out + (int64_t)tok * T::DIM + k0) = frag[0][ks];
-      *reinterpret_cast<bf16x8*>(pn_out + (int64_t)tok * T::DIM + k0) = frag[1][ks];
-    }
-    if (live && half == 0) {
-      q_inv[tok] = qi;
-      p_inv[tok] = pi;
-      s_pos_out[tok] = spos;
-    }
-  }
-  const float scale = clamp_scale(logit_scale_dev);
-  const float c1 = scale * LOG2E;
-  const bool do_logs = LOGS && (log_group < 0 || (int)blockIdx.z == log_group);
-
-  f32x16 u[ND];
-#pragma unroll
-  for (int dc = 0; dc < ND; ++dc) u[dc] = sg::zero16();
-  float sum = 0.f;
-  int nv = 0, rk = 0;
-
-  using P = sg::DmaPieces<NKS>;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  P dp;
-  dp.init(wv, lane);
-  const int t_last = n_tiles - 1;
-  auto dma_k = [&](auto k_c, auto slot_c, int tn) {
-    dp.template piece<decltype(k_c)::value>(smem + decltype(slot_c)::value * T::BYTES,
-                                             reinterpret_cast<const char*>(negs) + (int64_t)tn * (32 * T::ROW_BYTES));
-  };
-  auto dma_all = [&](auto slot_c, int tn) {
-    auto f = [&](auto k_c) { dma_k(k_c, slot_c, tn); };
-    sg::static_for<P::PW>(f);
-  };
-  sg::LaneAddr<NKS> la;
-  la.init(lane);
-  sg::TrAddr<NKS> ta;
-  ta.init(la, smem);
-  sg::RowAddr<NKS> ra;
-  ra.init(la, smem);
-  // slot 3 is the "previous tile" of the first iteration (E = 0 there): make it finite
-  for (int o = threadIdx.x * 16; o < T::BYTES; o += 256 * 16) *reinterpret_cast<f32x4*>(smem + 3 * T::BYTES + o) = f32x4{0.f, 0.f, 0.f, 0.f};
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // published by the first ring barrier
-  dma_all(std::integral_constant<int, 0>{}, 0);
-  dma_all(std::integral_constant<int, 1>{}, min(1, t_last));
-  // scalars first used inside the loop: touch them here, or hipcc places the `s_waitcnt lgkmcnt(0)` that covers their
-  // kernel-argument load INSIDE the loop body, where it drains the LDS read pipeline once per tile
-  asm volatile("" ::"s"(thres), "s"(c1), "s"(tok_cap), "s"(n_neg));
-  // S / f accumulators ping-pong by tile parity: tile t's epilogue runs one iteration later, straight from the other set
-  f32x16 sf[2][2] = {{sg::zero16(), sg::zero16()}, {sg::zero16(), sg::zero16()}};
-  uint32_t alive_prev = 0;               // live-row bits of the previous tile, pre-shifted by 4*half
-  uint32_t my_word = 0, other_word = 0;  // suppression bits of the tile before the previous one (store pending)
-  // the loop exists twice (with / without the rank + n_valid counting of the logged group): a per-element runtime test
-  // would put a branch into every MFMA gap
-  STAMP_DECL
-  STAMP(-1)
-  auto run = [&](auto logs_c) {
-    constexpr bool WITH_LOGS = decltype(logs_c)::value;
-    sg::ring_loop<4>(n_tiles + 1, [&](auto slot_c, int i) {
-      constexpr int cur = decltype(slot_c)::value, nxt = (cur + 2) % 4, prv = (cur + 3) % 4, par = cur & 1;
-      STAMP(2)
-      sg::wait_vmcnt<P::PW>();
-      STAMP(0)
-      sg::ring_barrier();
-      STAMP(1)
-      const int tn = min(i + 2, t_last);
-      sf[par][0] = sg::zero16();
-      sf[par][1] = sg::zero16();
-      const f32x16& s_prev = sf[par ^ 1][0];
-      const f32x16& f_cur = sf[par][1];
-      uint32_t sbits = 0;                  // false negatives of THIS tile (bit (g&3)+8(g>>2) = accumulator row g of my half)
-      sg::tile_step<NKS, ND, cur * T::BYTES, prv * T::BYTES, P::PW, 2>(
-          ra, ta, frag, sf[par], u, [](auto) {},
-          [&](int g) {                     // gated logit of the previous tile: alive_prev already excludes its false negatives
-            const float ek = gate_alive(s_prev[g], c1, c1, alive_prev, (g & 3) + 8 * (g >> 2));
-            asm volatile("v_add_f32 %0, %0, %1" : "+v"(sum) : "v"(ek));      // volatile: keep the accumulation in this gap
-            if constexpr (WITH_LOGS) {
-              const int pos = (g & 3) + 8 * (g >> 2);
-              const int km = ((int)(alive_prev << (31 - pos))) >> 31;       // -1: a kept, live logit
-              nv -= km;
-              rk -= s_prev[g] > spos ? km : 0;
-            }
-            return ek;
-          },
-          [&](auto k_c) {                  // gaps of the second product: next tile's DMA + this tile's suppression tests
-            constexpr int k = decltype(k_c)::value;
-            if constexpr (k < P::PW) dma_k(k_c, std::integral_constant<int, nxt>{}, tn);
-            uint32_t& sb = sbits;         // (named here: an asm operand alone does not capture it in a generic lambda)
-            // the 16 tests are spread over gaps 2 .. 2 ND - 1: the first two gaps still wait for the f accumulator chain
-            constexpr int G = 2 * ND - 2;
-            constexpr int g_lo = G > 0 ? (k >= 2 ? (k - 2) * 16 / G : 0) : 0;
-            constexpr int g_hi = G > 0 ? (k >= 2 ? (k - 1) * 16 / G : 0) : (k == 2 * ND - 1 ? 16 : 0);
-#pragma unroll
-            for (int g = g_lo; g < g_hi; ++g) {
-              const int sm = f_cur[g] > thres ? -1 : 0;                      // false negative: cos(positive, negative) > thres
-              asm volatile("v_and_or_b32 %0, %1, %2, %0" : "+v"(sb) : "v"(sm), "s"(1u << ((g & 3) + 8 * (g >> 2))));
-            }
-          },
-          sg::EpiIdentity{}, [&] { STAMP(3) });
-      STAMP(4)
-      // suppression word of this tile (bit j = negative 32 i + j suppressed for my token): the two lane halves hold
-      // disjoint bits; the cross-half exchange is issued here and consumed (stored) at the top of the next iteration
-      if (i > 0 && in_cap && half == 0) supp_out[(int64_t)(i - 1) * tok_cap + tok] = live ? (my_word | other_word) : 0xFFFFFFFFu;
-      my_word = sbits << (4 * half);
-      other_word = __shfl_xor(my_word, 32, 64);
-      const int rem = n_neg - i * 32;
-      const uint32_t tail = rem >= 32 ? 0xFFFFFFFFu : (rem > 0 ? ~(0xFFFFFFFFu << rem) : 0u);
-      alive_prev = (live && i < n_tiles) ? ((tail >> (4 * half)) & ~sbits) : 0u;
-    });
-  };
-  if (do_logs) run(std::true_type{});
-  else run(std::false_type{});
-  STAMP(2)
-  STAMP_FLUSH
-  sg::wait_vmcnt<0>();
-
-  sum += __shfl_xor(sum, 32, 64);
-  if (LOGS) {
-    nv += __shfl_xor(nv, 32, 64);
-    rk += __shfl_xor(rk, 32, 64);
-  }
-  if (live && half == 0) {
-    atomicAdd(sum_out + tok, sum);
-    if (do_logs) {
-      if (n_valid) atomicAdd(n_valid + tok, nv);
-      if (rank) atomicAdd(rank + tok, rk);
-    }
-  }
-  // U: rows (regs) = tokens wave*32 + crow(g, half), columns (lanes) = features dc*32 + r
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    const int tk = tok0 + wave * 32 + sg::crow(g, half);
-    if (tk < n_tok) {
-#pragma unroll
-      for (int dc = 0; dc < ND; ++dc) {
-        const int d = dc * 32 + r;
-        if (d < T::DIM) u_out[(int64_t)tk * T::DIM + d] = u[dc][g];
-      }
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -862,14 +502,23 @@ __global__ __launch_bounds__(256) void nce_fix_exact_kernel(const IT* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
-// fused forward, false-negative test hoisted out (training path, default)
+// fused forward: loss sums and the token-side backward product in one pass
 // ------------------------------------------------------------------------------------------
+// dQn_i = sum_j G_ij n_j with G_ij = w_i keep_ij exp(scale s_ij - lse_i) factorises as
+//     dQn_i = w_i exp(scale - lse_i) * U_i,     U_i = sum_j keep_ij exp(scale (s_ij - 1)) n_j ,
+// and U_i needs neither lse nor w: it is the numerator that goes with the softmax denominator the forward already
+// accumulates (the flash-attention output accumulator without the running max - |logit| <= scale bounds the
+// exponent).  So the forward keeps a second accumulator U [32 tokens x D] per wave and feeds the gated tile
+// E = keep * exp(scale (s - 1)) (bf16, in registers) straight back into the matrix pipe against the SAME LDS tile
+// (transposed fragments); what is left of the token-side backward is a row-wise kernel (nce_bwd_rows_kernel below).
+// One wave per SIMD (U is 128 accumulator registers), 4-slot DMA ring, hand-ordered tile step (sg::tile_step_pf).
+//
 // cos(target, negative) > thres depends on the TARGET ROW, not on the token: at cfg1 every target row is the positive of up
-// to P = 8 (position, offset) tokens per category, so nce_fwd_u_kernel evaluates the same f = p.n product up to 8 times.
-// Here nce_fix_bits_kernel computes it once per (group, target row, negative) and leaves one bit per pair; this kernel
-// then carries ONE stationary fragment set (the query: 64 VGPRs fewer), 16 instead of 32 MFMAs in the S phase, no compare
-// chain - the tile's 32 suppression bits of a token arrive as one LDS-DMA word per lane, gathered by target row, riding the
-// same ring (one more piece per tile) - and the saved per-token suppression words for nce_bwd_n are that very word.
+// to P = 8 (position, offset) tokens per category.  nce_fix_bits_kernel computes f = p.n once per (group, target row,
+// negative) and leaves one bit per pair, so this kernel carries ONE stationary fragment set (the query), 16 MFMAs in the
+// S phase and no compare chain - the tile's 32 suppression bits of a token arrive as one LDS-DMA word per lane, gathered by
+// target row, riding the same ring (one more piece per tile) - and the saved per-token suppression words for nce_bwd_n are
+// that very word.  SUPP = false is the plain form: no bit table, no words, nothing suppressed.
 template <int NKS, typename IT, bool LOGS, bool SUPP = true>
 __global__ __launch_bounds__(256, 1) void nce_fwd_d_kernel(const IT* __restrict__ q_rows, const int32_t* q_idx,
                                                            const IT* __restrict__ p_rows, const int32_t* p_idx,
@@ -932,7 +581,9 @@ __global__ __launch_bounds__(256, 1) void nce_fwd_d_kernel(const IT* __restrict_
         *reinterpret_cast<bf16x8*>(pn_out + (int64_t)tok * T::DIM + ks * 16 + 8 * half) = pfrag[ks];
     }
   }
-  // saved state; lanes past n_tok inside the block write zero rows / all-ones suppression words (see nce_fwd_kernel)
+  // Saved state for the backward.  Lanes past n_tok inside a processed block (tok < tok_cap) are written too - zero rows
+  // here and all-ones suppression words in the loop - so that the backward can stream whole 32-token tiles without
+  // clamping: a padded token contributes exactly nothing.
   if (in_cap) {
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
@@ -1094,7 +745,7 @@ __global__ __launch_bounds__(256, 1) void nce_fwd_d_kernel(const IT* __restrict_
   }
 }
 
-// lse / loss from the partial sums of all negative ranges
+// lse / loss from the per-token sums of the forward
 constexpr int MAX_BUCKETS = 64;
 __global__ __launch_bounds__(256) void nce_finalize_kernel(const float* sum, const float* s_pos,
                                                            const int32_t* __restrict__ n_tok_dev, int tok_cap,
@@ -1156,7 +807,7 @@ __device__ __forceinline__ float half_sum(float v) {   // sum over the 32 lanes 
   return v;
 }
 
-// Row-wise remainder of the token-side backward: dQn_i = w_i exp(scale - lse_i) U_i (U from nce_fwd_u_kernel), the
+// Row-wise remainder of the token-side backward: dQn_i = w_i exp(scale - lse_i) U_i (U from nce_fwd_d_kernel), the
 // positive-pair term, the L2-normalisation chain rule, d(logit_scale), and the accumulation into the shared source
 // rows.  One wave per token, four tokens in flight per wave; lanes cover the feature dim 64 at a time (256-B float
 // atomic segments).  Also writes lw = lse log2(e) - log2(w) for nce_bwd_n.
@@ -1290,7 +941,7 @@ __global__ __launch_bounds__(256, 1) void nce_bwd_n_kernel(const bf16_t* qn, con
   constexpr int ND = (NKS + 1) / 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // per ring slot: Q tile | [4 waves][64] words: lanes 0-31 = suppression words of that wave's negative tile for the
-  // 32 tokens, lanes 32-63 = lw (= lse log2e - log2 w, written by nce_bwd_q) of the 32 tokens
+  // 32 tokens, lanes 32-63 = lw (= lse log2e - log2 w, written by nce_bwd_rows_kernel) of the 32 tokens
   constexpr int BUF = T::BYTES + 1024;
   using P = sg::DmaPieces<NKS>;
   {
@@ -1324,7 +975,7 @@ __global__ __launch_bounds__(256, 1) void nce_bwd_n_kernel(const bf16_t* qn, con
 #pragma unroll
   for (int dc = 0; dc < ND; ++dc) dn[dc] = sg::zero16();
 
-  // Token tiles stream like the negative tiles of nce_bwd_q (same branch-free ring).  tok_cap is a multiple of 32 and
+  // Token tiles stream like the negative tiles of nce_fwd_d_kernel (same branch-free ring).  tok_cap is a multiple of 32 and
   // the forward pads the last live 32-token tile (zero Qn rows, all-ones suppression words), so no row is ever
   // clamped and a padded token contributes exactly nothing.
   P dp;
@@ -1448,14 +1099,39 @@ inline bool nks_for(int dim, int& nks) {
     default: MACRO(16); break; \
   }
 
-static inline int nce_splits(int n_tiles, int n_groups, int want, int& tiles_per_split) {
-  // (token block, negative range, group) units should outnumber the ~512 workgroup slots several times; groups
-  // already multiply the unit count, so fewer negative ranges are needed (each range repeats the prologue/epilogue)
-  int splits = want / (n_groups > 0 ? n_groups : 1);
-  if (splits < 1) splits = 1;
-  while (splits > 1 && n_tiles / splits < 32) splits >>= 1;
-  tiles_per_split = (n_tiles + splits - 1) / splits;
-  return (n_tiles + tiles_per_split - 1) / tiles_per_split;
+// Launch geometry of nce_fix_bits_kernel (the prefix pass of the filtered form runs on the same grid): 256 target rows per
+// workgroup, the negative tiles cut into up to 8 slices so that the 512 workgroup slots are filled about twice over.
+struct FixBitsGrid {
+  int n_rows_pad, slices, tiles_per_slice;
+  dim3 grid(int n_groups) const { return dim3(n_rows_pad / 256, slices, n_groups); }
+};
+static inline FixBitsGrid fix_bits_grid(int64_t n_p_rows, int n_neg, int n_groups) {
+  const int n_tiles = (n_neg + 31) / 32;
+  FixBitsGrid g;
+  g.n_rows_pad = (int)((n_p_rows + 255) / 256 * 256);
+  g.slices = 1;
+  while (g.slices < 8 && (g.n_rows_pad / 256) * n_groups * g.slices < 768 && n_tiles / (g.slices * 2) >= 16) g.slices *= 2;
+  g.tiles_per_slice = (n_tiles + g.slices - 1) / g.slices;
+  return g;
+}
+
+template <int NKS, typename IT>
+static void launch_fix_bits(hipStream_t s, const void* p_rows, int64_t n_p_rows, const void* negs, int n_neg, int n_groups,
+                            float thres, uint32_t* fix_words, const int32_t* fix_row_list, const int32_t* fix_n_rows,
+                            int32_t* fix_slot_of_row, int32_t* fix_any) {
+  const FixBitsGrid g = fix_bits_grid(n_p_rows, n_neg, n_groups);
+  hipLaunchKernelGGL((nce_fix_bits_kernel<NKS, IT>), g.grid(n_groups), dim3(256), 3 * sg::Tile<NKS>::BYTES, s, (const IT*)p_rows,
+                     (int)n_p_rows, (const bf16_t*)negs, n_neg, thres, fix_words, g.n_rows_pad, g.tiles_per_slice, fix_row_list,
+                     fix_n_rows, fix_slot_of_row, fix_any);
+}
+
+// nce_fwd_d_kernel on its grid: 128 tokens per workgroup, 4 tile slots and 4 x 1 KiB of suppression words in LDS.
+// `rest` is the kernel's argument list from p_idx on.
+template <int NKS, typename IT, bool LOGS, bool SUPP, typename... Rest>
+static void launch_fwd_d(hipStream_t s, int tok_cap, int n_groups, const void* q_rows, const int32_t* q_idx, const void* p_rows,
+                         Rest... rest) {
+  hipLaunchKernelGGL((nce_fwd_d_kernel<NKS, IT, LOGS, SUPP>), dim3((tok_cap + 127) / 128, 1, n_groups), dim3(256),
+                     4 * sg::Tile<NKS>::BYTES + 4 * 1024, s, (const IT*)q_rows, q_idx, (const IT*)p_rows, rest...);
 }
 
 extern "C" int mhr_nce_fwd(const void* q_rows, const int32_t* q_idx, const void* p_rows, const int32_t* p_idx, int io_dtype,
@@ -1466,111 +1142,50 @@ extern "C" int mhr_nce_fwd(const void* q_rows, const int32_t* q_idx, const void*
                            const int32_t* fix_n_rows, int32_t* fix_slot_of_row, void* stream) {
   MHR_REQUIRE(q_rows && q_idx && p_rows && p_idx && negs && n_tok_dev && logit_scale_dev && sum_out && s_pos,
               "nce_fwd: null pointer");
-  MHR_REQUIRE(!fix_words || (u_out && n_p_rows > 0 && n_p_rows < (1ll << 31) - 256), "nce_fwd: fix_words needs u_out and n_p_rows");
+  // two forms (include/mhr.h): hoisted = bit table + fused forward, plain = fused forward with nothing suppressed
+  MHR_REQUIRE(u_out, "nce_fwd: u_out = NULL asks for the non-fused forward (negative splits over grid.y), which was removed; "
+                     "the fused forward always writes U");
+  const bool hoisted = fix_words && supp_out, plain = !fix_words && !supp_out;
+  MHR_REQUIRE(fix_words || !supp_out, "nce_fwd: supp_out without fix_words asks for the fused forward with the per-token "
+                                      "false-negative test, which was removed; pass fix_words (hoisted form)");
+  MHR_REQUIRE(hoisted || plain, "nce_fwd: fix_words needs supp_out (hoisted form); the plain form takes neither");
+  MHR_REQUIRE(!hoisted || (n_p_rows > 0 && n_p_rows < (1ll << 31) - 256), "nce_fwd: fix_words needs n_p_rows");
   MHR_REQUIRE((fix_row_list != nullptr) == (fix_n_rows != nullptr) && (fix_row_list != nullptr) == (fix_slot_of_row != nullptr) &&
                   (!fix_row_list || fix_words),
               "nce_fwd: fix_row_list, fix_n_rows and fix_slot_of_row go together (and need fix_words)");
-  const bool plain = u_out && !fix_words && !supp_out;     // fused forward with NOTHING suppressed (row-sharing path)
-  MHR_REQUIRE(!u_out || (qn_out && q_inv && p_inv && tok_cap % 32 == 0 && (plain || (pn_out && supp_out))),
-              "nce_fwd: u_out (fused training path) needs every saved tensor and tok_cap %% 32 == 0");
-  MHR_REQUIRE(!plain || n_neg % 32 == 0, "nce_fwd: the no-suppression form (supp_out = fix_words = NULL) needs n_neg %% 32 == 0");
+  MHR_REQUIRE(qn_out && q_inv && p_inv && tok_cap % 32 == 0 && (plain || pn_out),
+              "nce_fwd: needs every saved tensor and tok_cap %% 32 == 0");
+  MHR_REQUIRE(!plain || n_neg % 32 == 0, "nce_fwd: the plain form (supp_out = fix_words = NULL) needs n_neg %% 32 == 0");
   int nks;
   MHR_REQUIRE(nks_for(dim, nks), "nce_fwd: dim=%d unsupported (16/32/64/128/256)", dim);
   MHR_REQUIRE(n_neg > 0 && tok_cap > 0 && n_groups >= 1 && n_groups <= 65535, "nce_fwd: bad sizes");
-  int tps;
-  const int splits = nce_splits((n_neg + 31) / 32, n_groups, 4, tps);
-  const dim3 grid((tok_cap + 127) / 128, splits, n_groups);
   hipStream_t s = (hipStream_t)stream;
   const bool logs = n_valid != nullptr || rank != nullptr;
-#define ARGS(IT)                                                                                                         \
-  (const IT*)q_rows, q_idx, (const IT*)p_rows, p_idx, (const bf16_t*)negs, n_neg, n_tok_dev, tok_cap, logit_scale_dev,   \
-      thres, tps, sum_out, n_valid, rank, (bf16_t*)qn_out, (bf16_t*)pn_out, supp_out, q_inv, p_inv, s_pos, log_group
-#define LU_(NKS)                                                                                                         \
+  const int n_rows_pad = hoisted ? fix_bits_grid(n_p_rows, n_neg, n_groups).n_rows_pad : 0;
+#define FWD_D(NKS, IT, LOGS, SUPP)                                                                                       \
+  launch_fwd_d<NKS, IT, LOGS, SUPP>(s, tok_cap, n_groups, q_rows, q_idx, p_rows, p_idx, (const bf16_t*)negs, n_neg, n_tok_dev,   \
+                                    tok_cap, logit_scale_dev, thres, sum_out, n_valid, rank, (bf16_t*)qn_out, (bf16_t*)pn_out, \
+                                    supp_out, q_inv, p_inv, s_pos, log_group, u_out, (const uint32_t*)fix_words, n_rows_pad, \
+                                    (const int32_t*)fix_slot_of_row, hoisted ? (int)n_p_rows : 0)
+#define LD2_(NKS, IT)                                                                                                    \
   {                                                                                                                      \
-    size_t lds = 4 * sg::Tile<NKS>::BYTES;                                                                               \
-    const dim3 gu((tok_cap + 127) / 128, 1, n_groups);                                                                   \
-    if (io_dtype == MHR_BF16) {                                                                                          \
-      if (logs) hipLaunchKernelGGL((nce_fwd_u_kernel<NKS, bf16_t, true>), gu, dim3(256), lds, s, UARGS(bf16_t));         \
-      else hipLaunchKernelGGL((nce_fwd_u_kernel<NKS, bf16_t, false>), gu, dim3(256), lds, s, UARGS(bf16_t));             \
+    if (hoisted) {                                                                                                       \
+      launch_fix_bits<NKS, IT>(s, p_rows, n_p_rows, negs, n_neg, n_groups, thres, fix_words, fix_row_list, fix_n_rows,   \
+                               fix_slot_of_row, nullptr);                                                                \
+      if (logs) FWD_D(NKS, IT, true, true); else FWD_D(NKS, IT, false, true);                                            \
     } else {                                                                                                             \
-      if (logs) hipLaunchKernelGGL((nce_fwd_u_kernel<NKS, float, true>), gu, dim3(256), lds, s, UARGS(float));           \
-      else hipLaunchKernelGGL((nce_fwd_u_kernel<NKS, float, false>), gu, dim3(256), lds, s, UARGS(float));               \
+      if (logs) FWD_D(NKS, IT, true, false); else FWD_D(NKS, IT, false, false);                                          \
     }                                                                                                                    \
   }
-#define UARGS(IT)                                                                                                        \
-  (const IT*)q_rows, q_idx, (const IT*)p_rows, p_idx, (const bf16_t*)negs, n_neg, n_tok_dev, tok_cap, logit_scale_dev,   \
-      thres, sum_out, n_valid, rank, (bf16_t*)qn_out, (bf16_t*)pn_out, supp_out, q_inv, p_inv, s_pos, log_group, u_out
-  if (u_out && fix_words) {
-    // false-negative bits once per (group, target row, negative), then the fused forward with one stationary operand
-    const int n_tiles = (n_neg + 31) / 32, n_rows_pad = (int)((n_p_rows + 255) / 256 * 256);
-    int slices = 1;                       // fill the 512 workgroup slots about twice over
-    while (slices < 8 && (n_rows_pad / 256) * n_groups * slices < 768 && n_tiles / (slices * 2) >= 16) slices *= 2;
-    const int tps_f = (n_tiles + slices - 1) / slices;
-#define LF_(NKS)                                                                                                         \
+#define LD_(NKS)                                                                                                         \
   {                                                                                                                      \
-    const dim3 gf(n_rows_pad / 256, slices, n_groups);                                                                   \
-    const size_t ldsf = 3 * sg::Tile<NKS>::BYTES;                                                                        \
-    const size_t ldsd = 4 * sg::Tile<NKS>::BYTES + 4 * 1024;                                                             \
-    const dim3 gu((tok_cap + 127) / 128, 1, n_groups);                                                                   \
-    if (io_dtype == MHR_BF16) {                                                                                          \
-      hipLaunchKernelGGL((nce_fix_bits_kernel<NKS, bf16_t>), gf, dim3(256), ldsf, s, (const bf16_t*)p_rows, (int)n_p_rows, \
-                         (const bf16_t*)negs, n_neg, thres, fix_words, n_rows_pad, tps_f, fix_row_list, fix_n_rows,     \
-                         fix_slot_of_row, (int32_t*)nullptr);                                                            \
-      if (logs) hipLaunchKernelGGL((nce_fwd_d_kernel<NKS, bf16_t, true>), gu, dim3(256), ldsd, s, UARGS(bf16_t), fix_words, n_rows_pad, fix_slot_of_row, (int)n_p_rows); \
-      else hipLaunchKernelGGL((nce_fwd_d_kernel<NKS, bf16_t, false>), gu, dim3(256), ldsd, s, UARGS(bf16_t), fix_words, n_rows_pad, fix_slot_of_row, (int)n_p_rows);     \
-    } else {                                                                                                             \
-      hipLaunchKernelGGL((nce_fix_bits_kernel<NKS, float>), gf, dim3(256), ldsf, s, (const float*)p_rows, (int)n_p_rows, \
-                         (const bf16_t*)negs, n_neg, thres, fix_words, n_rows_pad, tps_f, fix_row_list, fix_n_rows,     \
-                         fix_slot_of_row, (int32_t*)nullptr);                                                            \
-      if (logs) hipLaunchKernelGGL((nce_fwd_d_kernel<NKS, float, true>), gu, dim3(256), ldsd, s, UARGS(float), fix_words, n_rows_pad, fix_slot_of_row, (int)n_p_rows); \
-      else hipLaunchKernelGGL((nce_fwd_d_kernel<NKS, float, false>), gu, dim3(256), ldsd, s, UARGS(float), fix_words, n_rows_pad, fix_slot_of_row, (int)n_p_rows);     \
-    }                                                                                                                    \
+    if (io_dtype == MHR_BF16) LD2_(NKS, bf16_t) else LD2_(NKS, float)                                                    \
   }
-    NKS_SWITCH(nks, LF_);
-#undef LF_
-    MHR_CHECK_LAUNCH("nce_fwd (fused, hoisted false-negative test)");
-    return MHR_OK;
-  }
-  if (plain) {
-#define LP_(NKS)                                                                                                         \
-  {                                                                                                                      \
-    const size_t ldsd = 4 * sg::Tile<NKS>::BYTES + 4 * 1024;                                                             \
-    const dim3 gu((tok_cap + 127) / 128, 1, n_groups);                                                                   \
-    if (io_dtype == MHR_BF16) {                                                                                          \
-      if (logs) hipLaunchKernelGGL((nce_fwd_d_kernel<NKS, bf16_t, true, false>), gu, dim3(256), ldsd, s, UARGS(bf16_t), (const uint32_t*)nullptr, 0, (const int32_t*)nullptr, 0); \
-      else hipLaunchKernelGGL((nce_fwd_d_kernel<NKS, bf16_t, false, false>), gu, dim3(256), ldsd, s, UARGS(bf16_t), (const uint32_t*)nullptr, 0, (const int32_t*)nullptr, 0);     \
-    } else {                                                                                                             \
-      if (logs) hipLaunchKernelGGL((nce_fwd_d_kernel<NKS, float, true, false>), gu, dim3(256), ldsd, s, UARGS(float), (const uint32_t*)nullptr, 0, (const int32_t*)nullptr, 0); \
-      else hipLaunchKernelGGL((nce_fwd_d_kernel<NKS, float, false, false>), gu, dim3(256), ldsd, s, UARGS(float), (const uint32_t*)nullptr, 0, (const int32_t*)nullptr, 0);     \
-    }                                                                                                                    \
-  }
-    NKS_SWITCH(nks, LP_);
-#undef LP_
-    MHR_CHECK_LAUNCH("nce_fwd (fused, nothing suppressed)");
-    return MHR_OK;
-  }
-  if (u_out) {
-    NKS_SWITCH(nks, LU_);
-    MHR_CHECK_LAUNCH("nce_fwd (fused)");
-    return MHR_OK;
-  }
-#define L_(NKS)                                                                                                          \
-  {                                                                                                                      \
-    size_t lds = 3 * sg::Tile<NKS>::BYTES;                                                                               \
-    if (io_dtype == MHR_BF16) {                                                                                          \
-      if (logs) hipLaunchKernelGGL((nce_fwd_kernel<NKS, bf16_t, true>), grid, dim3(256), lds, s, ARGS(bf16_t));          \
-      else hipLaunchKernelGGL((nce_fwd_kernel<NKS, bf16_t, false>), grid, dim3(256), lds, s, ARGS(bf16_t));              \
-    } else {                                                                                                             \
-      if (logs) hipLaunchKernelGGL((nce_fwd_kernel<NKS, float, true>), grid, dim3(256), lds, s, ARGS(float));            \
-      else hipLaunchKernelGGL((nce_fwd_kernel<NKS, float, false>), grid, dim3(256), lds, s, ARGS(float));                \
-    }                                                                                                                    \
-  }
-  NKS_SWITCH(nks, L_);
-#undef L_
-#undef LU_
-#undef ARGS
-#undef UARGS
-  MHR_CHECK_LAUNCH("nce_fwd");
+  NKS_SWITCH(nks, LD_);
+#undef LD_
+#undef LD2_
+#undef FWD_D
+  MHR_CHECK_LAUNCH(hoisted ? "nce_fwd (hoisted false-negative test)" : "nce_fwd (nothing suppressed)");
   return MHR_OK;
 }
 
@@ -1584,25 +1199,15 @@ extern "C" int mhr_nce_fix_bits(const void* p_rows, int io_dtype, int64_t n_p_ro
   MHR_REQUIRE(nks_for(dim, nks), "nce_fix_bits: dim=%d unsupported (16/32/64/128/256)", dim);
   MHR_REQUIRE(n_neg > 0 && n_p_rows > 0 && n_groups >= 1 && n_groups <= 65535, "nce_fix_bits: bad sizes");
   hipStream_t s = (hipStream_t)stream;
-  const int n_tiles = (n_neg + 31) / 32, n_rows_pad = (int)((n_p_rows + 255) / 256 * 256);
-  int slices = 1;                       // fill the 512 workgroup slots about twice over
-  while (slices < 8 && (n_rows_pad / 256) * n_groups * slices < 768 && n_tiles / (slices * 2) >= 16) slices *= 2;
-  const int tps_f = (n_tiles + slices - 1) / slices;
-#define LFB_(NKS)                                                                                                        \
-  {                                                                                                                      \
-    const dim3 gf(n_rows_pad / 256, slices, n_groups);                                                                   \
-    const size_t ldsf = 3 * sg::Tile<NKS>::BYTES;                                                                        \
-    if (io_dtype == MHR_BF16)                                                                                            \
-      hipLaunchKernelGGL((nce_fix_bits_kernel<NKS, bf16_t>), gf, dim3(256), ldsf, s, (const bf16_t*)p_rows, (int)n_p_rows, \
-                         (const bf16_t*)negs, n_neg, thres, fix_words, n_rows_pad, tps_f, fix_row_list, fix_n_rows,     \
-                         fix_slot_of_row, fix_any);                                                                      \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((nce_fix_bits_kernel<NKS, float>), gf, dim3(256), ldsf, s, (const float*)p_rows, (int)n_p_rows, \
-                         (const bf16_t*)negs, n_neg, thres, fix_words, n_rows_pad, tps_f, fix_row_list, fix_n_rows,     \
-                         fix_slot_of_row, fix_any);                                                                      \
+#define LFB2_(NKS, IT) \
+  launch_fix_bits<NKS, IT>(s, p_rows, n_p_rows, negs, n_neg, n_groups, thres, fix_words, fix_row_list, fix_n_rows, fix_slot_of_row, fix_any)
+#define LFB_(NKS)                                                              \
+  {                                                                            \
+    if (io_dtype == MHR_BF16) LFB2_(NKS, bf16_t); else LFB2_(NKS, float);      \
   }
   NKS_SWITCH(nks, LFB_);
 #undef LFB_
+#undef LFB2_
   MHR_CHECK_LAUNCH("nce_fix_bits");
   return MHR_OK;
 }
@@ -1632,7 +1237,7 @@ extern "C" int mhr_nce_fix_bits_filtered(const void* p_rows, int io_dtype, int64
   MHR_REQUIRE(n_neg > 0 && n_p_rows > 0 && n_p_rows < (1ll << 31) - 256 && n_groups >= 1 && n_groups <= 65535,
               "nce_fix_bits_filtered: bad sizes");
   const int nks = dim / 16;
-  const int n_tiles = (n_neg + 31) / 32, n_rows_pad = (int)((n_p_rows + 255) / 256 * 256);
+  const int n_tiles = (n_neg + 31) / 32;
   const int64_t cap = fix_filter_cand_cap(n_p_rows, n_tiles, n_groups);
   MHR_REQUIRE(cap < (1ll << 31), "nce_fix_bits_filtered: %lld (group, row fragment, tile) units do not fit the int32 candidate codes",
               (long long)cap);
@@ -1643,21 +1248,19 @@ extern "C" int mhr_nce_fix_bits_filtered(const void* p_rows, int io_dtype, int64
   float* b_rem = (float*)((char*)workspace + 16);
   float* b_full = b_rem + (int64_t)n_groups * n_tiles;
   int32_t* cand = (int32_t*)((char*)workspace + fix_filter_tables_bytes(n_tiles, n_groups));
-  int slices = 1;                       // the exhaustive kernel's grid
-  while (slices < 8 && (n_rows_pad / 256) * n_groups * slices < 768 && n_tiles / (slices * 2) >= 16) slices *= 2;
-  const int tps_f = (n_tiles + slices - 1) / slices;
+  const FixBitsGrid fg = fix_bits_grid(n_p_rows, n_neg, n_groups);     // the exhaustive kernel's grid
   int64_t nb_exact = (cap + 3) / 4;     // one wave per candidate at most; 512 workgroups grid-stride over longer lists
   if (nb_exact > 512) nb_exact = 512;
 #define LFF2_(NKS, IT)                                                                                                   \
   {                                                                                                                      \
     hipLaunchKernelGGL((nce_neg_tile_norms_kernel<NKS>), dim3((n_tiles + 3) / 4, n_groups), dim3(256), 0, s,            \
                        (const bf16_t*)negs, n_neg, b_rem, b_full, counter);                                              \
-    hipLaunchKernelGGL((nce_fix_prefix_kernel<NKS, IT>), dim3(n_rows_pad / 256, slices, n_groups), dim3(256),            \
+    hipLaunchKernelGGL((nce_fix_prefix_kernel<NKS, IT>), fg.grid(n_groups), dim3(256),            \
                        3 * FIX_SUB * sg::Tile<FIX_KPS>::BYTES, s, (const IT*)p_rows, (int)n_p_rows, (const bf16_t*)negs, n_neg,    \
-                       thres, fix_words, n_rows_pad, tps_f, fix_row_list, fix_n_rows, fix_slot_of_row,                   \
+                       thres, fix_words, fg.n_rows_pad, fg.tiles_per_slice, fix_row_list, fix_n_rows, fix_slot_of_row,                   \
                        (const float*)b_rem, (const float*)b_full, counter, cand);                                        \
     hipLaunchKernelGGL((nce_fix_exact_kernel<NKS, IT>), dim3((int)nb_exact), dim3(256), 0, s, (const IT*)p_rows,         \
-                       (int)n_p_rows, (const bf16_t*)negs, n_neg, thres, fix_words, n_rows_pad, fix_row_list,            \
+                       (int)n_p_rows, (const bf16_t*)negs, n_neg, thres, fix_words, fg.n_rows_pad, fix_row_list,            \
                        fix_n_rows, fix_any, (const int32_t*)counter, (const int32_t*)cand, (int)cap);                    \
   }
 #define LFF_(NKS)                                                                                                        \

@@ -267,70 +267,15 @@ __device__ __forceinline__ void mma_tile(const unsigned char* tile, const LaneAd
   }
 }
 
-// Same product with an independent VALU job pinned into the MFMA gaps: after the MFMA of k-step ks the caller's
-// epi(e) runs for accumulator elements e = ks*EPK .. ks*EPK+EPK-1 of ANOTHER (already complete) accumulator, and a
-// sched_barrier fixes that order.  At one wave per SIMD the in-order issue stage cannot overlap a batch of MFMAs with
-// VALU work that follows the batch in program order; placing one element's epilogue (~8 VALU, one v_exp) in each
-// 32-cycle MFMA gap hides it behind the matrix pipe (cdna guide: "budget every MFMA gap ... and place them").
-template <int NKS, int PF, typename Epi>
-__device__ __forceinline__ void mma_tile_epi(const unsigned char* tile, const LaneAddr<NKS>& la, const bf16x8 (&frag)[1][NKS],
-                                             f32x16& acc, Epi epi) {
-  constexpr int P = PF < NKS ? PF : NKS;
-  constexpr int NB = (NKS + P - 1) / P;
-  constexpr int EPK = (16 + NKS - 1) / NKS;                // accumulator elements handled per k-step
-  bf16x8 a[2][P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) a[0][j] = la.read_a(tile, j);
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    if (b + 1 < NB) {
-#pragma unroll
-      for (int j = 0; j < P; ++j)
-        if ((b + 1) * P + j < NKS) a[(b + 1) & 1][j] = la.read_a(tile, (b + 1) * P + j);
-    }
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      const int ks = b * P + j;
-      if (ks < NKS) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[b & 1][j], frag[0][ks], acc, 0, 0, 0);
-#pragma unroll
-        for (int e = 0; e < EPK; ++e)
-          if (ks * EPK + e < 16) epi(ks * EPK + e);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
-}
-
-// out[dc] += A(g0,g1) . tile^T-fragments: the second product of the backward kernels (sums over the tile's 32 rows).
-// g0/g1 are the two k-step fragments of the gated tile; B fragments come from LaneAddr::read_tr, read one dc ahead.
-template <int NKS, int ND>
-__device__ __forceinline__ void mma_tile_tr(const unsigned char* tile, const LaneAddr<NKS>& la, bf16x8 g0, bf16x8 g1,
-                                            f32x16 (&out)[ND]) {
-  bf16x8 b[2][2];
-  b[0][0] = la.read_tr(tile, 0, 0);
-  b[0][1] = la.read_tr(tile, 0, 1);
-#pragma unroll
-  for (int dc = 0; dc < ND; ++dc) {
-    if (dc + 1 < ND) {
-      b[(dc + 1) & 1][0] = la.read_tr(tile, dc + 1, 0);
-      b[(dc + 1) & 1][1] = la.read_tr(tile, dc + 1, 1);
-    }
-    out[dc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g0, b[dc & 1][0], out[dc], 0, 0, 0);
-    out[dc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g1, b[dc & 1][1], out[dc], 0, 0, 0);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// The same product with the transposed reads emitted as inline asm.  hipcc 7.2 guards every
-// __builtin_amdgcn_ds_read_tr16_b64 with `s_waitcnt vmcnt(0)` when LDS-DMA loads are in flight (it cannot prove the
-// read does not alias the DMA destination), which drains the whole prefetch ring once per tile - in the
-// sampled-softmax backward kernels that exposed a full L2/HBM round trip per 32 MFMAs.  The asm form carries no
-// memory operand, so only the counted waits of the ring remain.  The price is doing the LDS wait counting by hand:
-// reads are issued PD column chunks ahead and `s_waitcnt lgkmcnt(4*PD)` (4 reads per chunk) precedes each MFMA pair;
-// the waited registers are threaded through the wait statement as "+v" operands so the MFMAs cannot be hoisted
-// above it.  LDS instructions hipcc adds on its own only make the counted wait stricter, never weaker.
-//   lds_base : LDS byte address of the ring (see lds_addr()), OFF: compile-time byte offset of the tile in the ring.
+// Transposed reads as inline asm.  hipcc 7.2 guards every __builtin_amdgcn_ds_read_tr16_b64 with `s_waitcnt vmcnt(0)`
+// when LDS-DMA loads are in flight (it cannot prove the read does not alias the DMA destination), which drains the
+// whole prefetch ring once per tile - in the sampled-softmax kernels that exposed a full L2/HBM round trip per 32 MFMAs.
+// The asm form carries no memory operand, so only the counted waits of the ring remain.  The price is doing the LDS wait counting by hand
+// (tile_step_pf below): reads are issued ahead and a counted `s_waitcnt lgkmcnt(n)` precedes each MFMA; the waited
+// registers are threaded through the wait statement as "+v" operands so the MFMAs cannot be hoisted above it.  LDS
+// instructions hipcc adds on its own only make the counted wait stricter, never weaker.
+//   lds_addr() : LDS byte address of the ring; tile offsets inside the ring are compile-time immediates.
 // ---------------------------------------------------------------------------------------------------------
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -345,12 +290,6 @@ __device__ __forceinline__ u32x2 ds_read_tr_asm(uint32_t addr) {
   u32x2 v;
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(IMM));
   return v;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_lgkm(u32x2& a, u32x2& b, u32x2& c, u32x2& d) {
-  static_assert(N >= 0 && N <= 15, "lgkmcnt is 4 bits");
-  asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
 }
 
 template <int N>
@@ -380,45 +319,15 @@ __device__ __forceinline__ void static_for(F& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-template <int NKS, int ND, int OFF, int PD = 2>
-__device__ __forceinline__ void mma_tile_tr_asm(const TrAddr<NKS>& ta, bf16x8 g0, bf16x8 g1, f32x16 (&out)[ND]) {
-  using T = Tile<NKS>;
-  constexpr int P = PD < ND ? PD : ND;
-  u32x2 r[P + 1][4];      // [.][0,1] = rows +0/+8 of k-step 0, [.][2,3] = of k-step 1
-  auto issue = [&](auto dc_c) {
-    constexpr int dc = decltype(dc_c)::value;
-    constexpr int imm = OFF + 256 * (dc >> 2), s1 = 16 * T::ROW_BYTES;
-    u32x2* q = r[dc % (P + 1)];
-    q[0] = ds_read_tr_asm<imm>(ta.t[0][dc & 3]);
-    q[1] = ds_read_tr_asm<imm>(ta.t[1][dc & 3]);
-    q[2] = ds_read_tr_asm<imm + s1>(ta.t[0][dc & 3]);
-    q[3] = ds_read_tr_asm<imm + s1>(ta.t[1][dc & 3]);
-  };
-  auto step = [&](auto dc_c) {
-    constexpr int dc = decltype(dc_c)::value;
-    if constexpr (dc + P < ND) issue(std::integral_constant<int, dc + P>{});
-    constexpr int ahead = (ND - 1 - dc) < P ? (ND - 1 - dc) : P;     // chunks issued after this one
-    u32x2* q = r[dc % (P + 1)];
-    wait_lgkm<4 * ahead>(q[0], q[1], q[2], q[3]);
-    const u32x4 b0 = {q[0].x, q[0].y, q[1].x, q[1].y}, b1 = {q[2].x, q[2].y, q[3].x, q[3].y};
-    out[dc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g0, __builtin_bit_cast(bf16x8, b0), out[dc], 0, 0, 0);
-    out[dc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g1, __builtin_bit_cast(bf16x8, b1), out[dc], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  static_for<P>(issue);
-  static_for<ND>(step);
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// One tile step of the backward kernels, hand-ordered (everything that touches LDS is inline asm, so the only waits
-// are the counted ones written here):
+// One tile step of the fused forward and the negative-side backward (tile_step_pf below), hand-ordered (everything that
+// touches LDS is inline asm, so the only waits are the counted ones written here):
 //     S(t)   = tile_cur . frag^T            NKS chained MFMAs, row fragments read PA k-steps ahead,
-//     epi(e)                                 the caller's per-element epilogue of S(t-1), EPK elements per MFMA gap,
+//     epi(e)                                 the caller's per-element epilogue of S(t-1), spread over the MFMA gaps,
 //     out   += G(t-1) . tile_prv             ND x 2 MFMAs, transposed fragments read PT chunks ahead - the first PT
 //                                            chunks are already requested during the last S gaps, so the second
 //                                            product starts without an LDS round trip.
-// `mid()` runs after the first PA row reads are in flight (the place for the next tile's DMA issue: its issue cost
-// overlaps the LDS latency).  `pack(g0, g1)` converts the finished epilogue into the two A fragments of G(t-1).
+// The finished epilogue elements are converted pairwise into the two A fragments of G(t-1).
 // LDS return order is issue order, so `s_waitcnt lgkmcnt(n)` with n = reads issued after the one needed is exact.
 // ---------------------------------------------------------------------------------------------------------
 template <int IMM>
@@ -459,10 +368,6 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
 
-// epi(e) -> float : element e (accumulator register index) of the gated previous tile, already masked.
-// dma(k)          : called once in every gap k = 0..2*ND-1 of the second product (and for k up to NDMA-1 afterwards if
-//                   there are fewer gaps): those gaps carry only two transposed reads, so the caller places the next
-//                   tile's LDS-DMA instructions there (k < its DMA count) and any VALU work that does not fit the S gaps.
 // acc[f] (+)= tile . frag[f]^T like mma_tile, with the row-fragment reads as inline asm (PA k-steps ahead, counted
 // lgkmcnt waits) and one sched_barrier per k-step: hipcc's own schedule of the builtin form leaves the MFMAs waiting on
 // `s_waitcnt lgkmcnt(0)` after short read batches.  OFF: compile-time byte offset of the tile in the ring whose LDS
@@ -492,10 +397,10 @@ __device__ __forceinline__ void mma_tile_asm(const RowAddr<NKS>& ra, const bf16x
   static_for<NKS>(step);
 }
 
-// Values read from LDS by the caller's own inline-asm reads (issued BEFORE bwd_tile) must be passed through this after
-// the wait that covers them: an asm output looks "ready" to hipcc at the read itself, so ordinary code or non-volatile
-// asm consuming it could otherwise be scheduled above the wait.  `ready(n)` in bwd_tile is the place: n = LDS reads
-// issued after the caller's.
+// Values read from LDS by the caller's own inline-asm reads (the `tail()` reads of tile_step_pf) must be passed through this
+// after the wait that covers them: an asm output looks "ready" to hipcc at the read itself, so ordinary code or non-volatile
+// asm consuming it could otherwise be scheduled above the wait.  `ready(n)` of the next tile step is the place: n = LDS
+// reads issued after the caller's.
 template <typename V>
 __device__ __forceinline__ void redefine(V& v) {
   asm volatile("" : "+v"(v));
@@ -507,13 +412,6 @@ __device__ __forceinline__ void wait_lgkm_values(V&... v) {
   (redefine(v), ...);
 }
 
-struct EpiIdentity {
-  __device__ __forceinline__ float operator()(int, float g) const { return g; }
-};
-struct NoMid {
-  __device__ __forceinline__ void operator()() const {}
-};
-
 // One stationary fragment set, epilogue spread over BOTH products.  The gated tile G(t-1) enters the second product as two
 // A fragments: g0 = elements 0..7, g1 = elements 8..15.  Sweeping the second product as {all column chunks x g0} then
 // {all column chunks x g1} means g1 is not needed before the second sweep, so only HALF of the per-element epilogue has to
@@ -521,92 +419,16 @@ struct NoMid {
 // the second.  Stamped at D = 256 before the split: S phase 1040 cycles for 16 MFMAs (512 in the matrix pipe) - each gap
 // carried a whole element (fma, quarter-rate exp, bit test, mask, running sum, convert: ~34 issue cycles against a 32-cycle
 // MFMA) - while the gaps of the second product carried two LDS reads and, in 5 of 16, one DMA instruction.
-template <int NKS, int ND, int OFF_CUR, int OFF_PRV, int NDMA, typename Ready, typename Epi, typename DmaFn, typename Mid>
-__device__ __forceinline__ void tile_step_split(const RowAddr<NKS>& ra, const TrAddr<NKS>& ta, const bf16x8 (&frag)[1][NKS],
-                                                f32x16 (&accs)[1], f32x16 (&out)[ND], Ready ready, Epi epi, DmaFn dma, Mid mid) {
-  using T = Tile<NKS>;
-  constexpr int PA = NKS < 4 ? NKS : 4;
-  constexpr int NCH = 2 * ND;                         // transposed chunks (two reads each) in sweep order: c = sweep * ND + dc
-  constexpr int PT = NKS < 2 ? 1 : 2;                 // chunks requested ahead (NCH >= 2 always)
-  constexpr int ES = (8 + NKS - 1) / NKS;             // elements 0..7 per S gap
-  constexpr int EU = (8 + ND - 1) / ND;               // elements 8..15 per gap of the first sweep
-  constexpr int T0 = NKS - PT;                        // S step after which chunk 0 is requested
-  u32x4 a[PA + 1];
-  u32x2 r[PT + 1][2];
-  uint32_t pk[8];
-  float even = 0.f;
-  auto issue_a = [&](auto ks_c) {
-    constexpr int ks = decltype(ks_c)::value;
-    a[ks % (PA + 1)] = ds_read_b128_asm<OFF_CUR + 256 * (ks >> 3)>(ra.a[ks & 7]);
-  };
-  auto issue_t = [&](auto c_c) {
-    constexpr int c = decltype(c_c)::value, dc = c % ND, sw = c / ND;
-    constexpr int imm = OFF_PRV + 256 * (dc >> 2) + sw * 16 * T::ROW_BYTES;
-    u32x2* q = r[c % (PT + 1)];
-    q[0] = ds_read_tr_asm<imm>(ta.t[0][dc & 3]);
-    q[1] = ds_read_tr_asm<imm>(ta.t[1][dc & 3]);
-  };
-  auto element = [&](int e) {
-    const float g = epi(e);
-    if (e & 1) pk[e >> 1] = cvt_pk_bf16(even, g); else even = g;
-  };
-  static_for<PA>(issue_a);
-  ready(std::integral_constant<int, PA>{});
-  auto s_step = [&](auto ks_c) {
-    constexpr int ks = decltype(ks_c)::value;
-    if constexpr (ks + PA < NKS) issue_a(std::integral_constant<int, ks + PA>{});
-    constexpr int a_after = (ks + PA < NKS ? ks + PA : NKS - 1) - ks;
-    constexpr int t_chunks = ks > T0 ? ks - T0 : 0;
-    wait_lgkm1<a_after + 2 * t_chunks>(a[ks % (PA + 1)]);
-    const bf16x8 av = __builtin_bit_cast(bf16x8, a[ks % (PA + 1)]);
-    accs[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, frag[0][ks], accs[0], 0, 0, 0);
-#pragma unroll
-    for (int e = ks * ES; e < ks * ES + ES && e < 8; ++e) element(e);
-    if constexpr (ks >= T0) issue_t(std::integral_constant<int, ks - T0>{});
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  static_for<NKS>(s_step);
-  mid();
-  bf16x8 g0, g1;
-  {
-    const u32x4 g0v = {pk[0], pk[1], pk[2], pk[3]};
-    g0 = __builtin_bit_cast(bf16x8, g0v);
-  }
-  auto t_step = [&](auto c_c) {
-    constexpr int c = decltype(c_c)::value, dc = c % ND, sw = c / ND;
-    if constexpr (c + PT < NCH) issue_t(std::integral_constant<int, c + PT>{});
-    constexpr int ahead = (NCH - 1 - c) < PT ? (NCH - 1 - c) : PT;
-    u32x2* q = r[c % (PT + 1)];
-    wait_lgkm2<2 * ahead>(q[0], q[1]);
-    const u32x4 bv = {q[0].x, q[0].y, q[1].x, q[1].y};
-    if constexpr (sw == 0) {
-      out[dc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g0, __builtin_bit_cast(bf16x8, bv), out[dc], 0, 0, 0);
-#pragma unroll
-      for (int e = 8 + dc * EU; e < 8 + dc * EU + EU && e < 16; ++e) element(e);
-    } else {
-      if constexpr (dc == 0) {
-        const u32x4 g1v = {pk[4], pk[5], pk[6], pk[7]};
-        g1 = __builtin_bit_cast(bf16x8, g1v);
-      }
-      out[dc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g1, __builtin_bit_cast(bf16x8, bv), out[dc], 0, 0, 0);
-      dma(std::integral_constant<int, dc>{});
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  static_for<NCH>(t_step);
-  auto rest = [&](auto k_c) {
-    constexpr int k = decltype(k_c)::value;
-    if constexpr (k >= ND) dma(k_c);
-  };
-  static_for<NDMA>(rest);
-}
-
-// The split tile step with the NEXT tile's first row-fragment reads issued from its last gaps, for loops whose ring barrier sits
+//
+// The NEXT tile's first row-fragment reads are issued from the last gaps of the step, for loops whose ring barrier sits
 // in the MIDDLE of the step (`mid`, between the two products) instead of at the top.  With the barrier at the top every tile
 // began with an empty matrix pipe: counted DMA wait, barrier, then a full LDS round trip before the first MFMA (stamped: ~410
 // cycles of loop top + ~150 of wait / barrier per ~2250-cycle tile).  Here the barrier that publishes tile t + 1 is crossed
 // while tile t's second product still has its MFMAs to issue, the first PA fragments of tile t + 1 are requested in the last PA
 // gaps of that product, and the next step starts with them in flight.
+//   epi(e) -> float : element e (accumulator register index) of the gated previous tile, already masked
+//   dma(k) : called once in every gap k = 0..ND-1 of the second sweep (and for k up to NDMA-1 afterwards if there are fewer
+//            gaps): those gaps carry only two transposed reads, so the caller places the next tile's LDS-DMA instructions there
 //   a      : in/out, the PA prefetched fragments (k-steps 0..PA-1) of the tile at OFF_CUR on entry, of the tile at OFF_NXT on exit
 //   tail() : the caller's own LDS reads for the NEXT step (NW of them), issued right before the prefetch; `ready(PA)` of the next
 //            step waits for them (exactly PA reads are issued after them)
@@ -734,106 +556,6 @@ __device__ __forceinline__ void prefetch_first(const RowAddr<NKS>& ra, u32x4 (&a
   static_for<PA>(f);
 }
 
-// RF = 1: one stationary fragment set (the backward kernels).  RF = 2: two sets sharing every row-fragment read (the
-// fused forward: s = q.n and f = p.n); the per-element epilogue is then split over the two MFMA gaps of a k-step:
-// epi(e) after the first MFMA, epi2(e, value) after the second.
-template <int NKS, int ND, int OFF_CUR, int OFF_PRV, int NDMA, int RF, typename Ready, typename Epi, typename DmaFn,
-          typename Epi2 = EpiIdentity, typename Mid = NoMid>
-__device__ __forceinline__ void tile_step(const RowAddr<NKS>& ra, const TrAddr<NKS>& ta, const bf16x8 (&frag)[RF][NKS],
-                                          f32x16 (&accs)[RF], f32x16 (&out)[ND], Ready ready, Epi epi, DmaFn dma,
-                                          Epi2 epi2 = Epi2{}, Mid mid = Mid{}) {
-  if constexpr (RF == 1) {          // one stationary set: the split order (what follows is the RF = 2 order)
-    tile_step_split<NKS, ND, OFF_CUR, OFF_PRV, NDMA>(ra, ta, frag, accs, out, ready, epi, dma, mid);
-    return;
-  }
-  using T = Tile<NKS>;
-  constexpr int PA = NKS < 4 ? NKS : 4;
-  constexpr int PT = ND < 2 ? ND : 2;
-  constexpr int EPK = (16 + NKS - 1) / NKS;
-  constexpr int T0 = NKS - PT;             // S step after which transposed chunk 0 is requested
-  u32x4 a[PA + 1];
-  u32x2 r[PT + 1][4];
-  uint32_t pk[8];                          // bf16 pairs of the gated tile: pk[0..3] = k-step 0, pk[4..7] = k-step 1
-  float even = 0.f;
-  auto issue_a = [&](auto ks_c) {
-    constexpr int ks = decltype(ks_c)::value;
-    a[ks % (PA + 1)] = ds_read_b128_asm<OFF_CUR + 256 * (ks >> 3)>(ra.a[ks & 7]);
-  };
-  auto issue_t = [&](auto dc_c) {
-    constexpr int dc = decltype(dc_c)::value;
-    constexpr int imm = OFF_PRV + 256 * (dc >> 2), s1 = 16 * T::ROW_BYTES;
-    u32x2* q = r[dc % (PT + 1)];
-    q[0] = ds_read_tr_asm<imm>(ta.t[0][dc & 3]);
-    q[1] = ds_read_tr_asm<imm>(ta.t[1][dc & 3]);
-    q[2] = ds_read_tr_asm<imm + s1>(ta.t[0][dc & 3]);
-    q[3] = ds_read_tr_asm<imm + s1>(ta.t[1][dc & 3]);
-  };
-  static_for<PA>(issue_a);
-  ready(std::integral_constant<int, PA>{});
-  auto s_step = [&](auto ks_c) {
-    constexpr int ks = decltype(ks_c)::value;
-    if constexpr (ks + PA < NKS) issue_a(std::integral_constant<int, ks + PA>{});
-    constexpr int a_after = (ks + PA < NKS ? ks + PA : NKS - 1) - ks;
-    constexpr int t_chunks = ks > T0 ? ks - T0 : 0;
-    wait_lgkm1<a_after + 4 * t_chunks>(a[ks % (PA + 1)]);
-    const bf16x8 av = __builtin_bit_cast(bf16x8, a[ks % (PA + 1)]);
-    accs[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, frag[0][ks], accs[0], 0, 0, 0);
-    if constexpr (RF == 1) {
-#pragma unroll
-      for (int e = ks * EPK; e < ks * EPK + EPK && e < 16; ++e) {
-        const float g = epi(e);
-        if (e & 1) pk[e >> 1] = cvt_pk_bf16(even, g); else even = g;
-      }
-    } else {
-      float half_done[EPK];
-#pragma unroll
-      for (int e = ks * EPK; e < ks * EPK + EPK && e < 16; ++e) half_done[e - ks * EPK] = epi(e);
-      __builtin_amdgcn_sched_barrier(0);
-      accs[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, frag[1][ks], accs[1], 0, 0, 0);
-#pragma unroll
-      for (int e = ks * EPK; e < ks * EPK + EPK && e < 16; ++e) {
-        const float g = epi2(e, half_done[e - ks * EPK]);
-        if (e & 1) pk[e >> 1] = cvt_pk_bf16(even, g); else even = g;
-      }
-    }
-    if constexpr (ks >= T0) issue_t(std::integral_constant<int, ks - T0>{});
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  static_for<NKS>(s_step);
-  mid();                                   // (phase-timing hook of the stamped builds; nothing in the product)
-  const u32x4 g0v = {pk[0], pk[1], pk[2], pk[3]}, g1v = {pk[4], pk[5], pk[6], pk[7]};
-  const bf16x8 g0 = __builtin_bit_cast(bf16x8, g0v), g1 = __builtin_bit_cast(bf16x8, g1v);
-  auto t_step = [&](auto dc_c) {
-    constexpr int dc = decltype(dc_c)::value;
-    if constexpr (dc + PT < ND) issue_t(std::integral_constant<int, dc + PT>{});
-    constexpr int ahead = (ND - 1 - dc) < PT ? (ND - 1 - dc) : PT;
-    u32x2* q = r[dc % (PT + 1)];
-    wait_lgkm<4 * ahead>(q[0], q[1], q[2], q[3]);
-    const u32x4 b0 = {q[0].x, q[0].y, q[1].x, q[1].y}, b1 = {q[2].x, q[2].y, q[3].x, q[3].y};
-    out[dc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g0, __builtin_bit_cast(bf16x8, b0), out[dc], 0, 0, 0);
-    dma(std::integral_constant<int, 2 * dc>{});
-    __builtin_amdgcn_sched_barrier(0);
-    out[dc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g1, __builtin_bit_cast(bf16x8, b1), out[dc], 0, 0, 0);
-    dma(std::integral_constant<int, 2 * dc + 1>{});
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  static_for<ND>(t_step);
-  // callbacks beyond the 2*ND gaps (narrow feature dims have few gaps)
-  auto rest = [&](auto k_c) {
-    constexpr int k = decltype(k_c)::value;
-    if constexpr (k >= 2 * ND) dma(k_c);
-  };
-  static_for<NDMA>(rest);
-}
-
-template <int NKS, int ND, int OFF_CUR, int OFF_PRV, int NDMA, typename Ready, typename Epi, typename DmaFn>
-__device__ __forceinline__ void bwd_tile(const RowAddr<NKS>& ra, const TrAddr<NKS>& ta, const bf16x8 (&frag)[1][NKS],
-                                         f32x16& acc, f32x16 (&out)[ND], Ready ready, Epi epi, DmaFn dma) {
-  f32x16 accs[1] = {acc};
-  tile_step<NKS, ND, OFF_CUR, OFF_PRV, NDMA, 1>(ra, ta, frag, accs, out, ready, epi, dma);
-  acc = accs[0];
-}
-
 // Runs body(slot_constant, i) for i = 0..n-1 with slot = i % DEPTH as a COMPILE-TIME constant (the loop is unrolled
 // by the ring depth), so ring-slot bases fold into the immediate offset field of the LDS instructions.
 template <int DEPTH, typename Body>
@@ -843,19 +565,6 @@ __device__ __forceinline__ void ring_loop(int n, Body body) {
     if constexpr (DEPTH > 1) { if (i0 + 1 < n) body(std::integral_constant<int, 1>{}, i0 + 1); }
     if constexpr (DEPTH > 2) { if (i0 + 2 < n) body(std::integral_constant<int, 2>{}, i0 + 2); }
     if constexpr (DEPTH > 3) { if (i0 + 3 < n) body(std::integral_constant<int, 3>{}, i0 + 3); }
-  }
-}
-
-// Scheduling hint for a region that holds one 16-MFMA product (with its transposed LDS reads) and an independent
-// VALU epilogue: ask hipcc to emit them as 16 x {1 MFMA, 2 DS reads, `valu` VALU} so the epilogue runs in the issue
-// slots the matrix pipe leaves free (cdna guide T19; at one wave per SIMD nothing else can fill those slots).
-template <int VALU_PER_MFMA>
-__device__ __forceinline__ void interleave_mfma_valu_16() {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);              // MFMA
-    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);              // DS read
-    __builtin_amdgcn_sched_group_barrier(0x002, VALU_PER_MFMA, 0);  // VALU
   }
 }
 

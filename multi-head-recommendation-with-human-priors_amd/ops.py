@@ -748,7 +748,6 @@ _COUNTER_SCRATCH = {}
 STREAM_DIMS = (16, 32, 64, 128, 256)      # feature dims of the register-stationary streaming kernels
 
 
-HOIST_FALSE_NEGATIVE_TEST = os.environ.get("MHR_NCE_HOIST", "1") != "0"
 FILTER_FALSE_NEGATIVE_TEST = os.environ.get("MHR_NCE_FIX_FILTER", "1") != "0"    # 0: the exhaustive bit-table kernel
 
 
@@ -803,7 +802,23 @@ def _row_maps(q_idx, n_tok_dev, cap, row_cap):
     return r_q, tok2row, r_first, n_row
 
 
+def _p_row_lists(p_row_mask, G, n_p_rows, rp_pad):
+    """p_row_mask [G, n_p_rows] -> (row_list [G, rp_pad], n_list [G]): per group the rows of p_rows the mask names, compacted on
+    the device.  The bit-table kernels test only those rows (slot j of the list = column j of the table) and write the inverse
+    map, slot_of_row, themselves."""
+    assert p_row_mask.shape == (G, n_p_rows)
+    dev = p_row_mask.device
+    key = (G, n_p_rows, str(dev))
+    if key not in _ROW_IOTA:
+        ar = torch.arange(n_p_rows, dtype=torch.int32, device=dev)
+        _ROW_IOTA[key] = (ar[None].expand(G, -1).contiguous(), ar)
+    iota_g, iota = _ROW_IOTA[key]
+    row_list, _, _, n_list = token_compact(p_row_mask.contiguous(), iota_g, iota, iota, tok_cap=rp_pad)
+    return row_list, n_list
+
+
 def _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask):
+    """The false-negative bit table of the target rows, for the row-sharing path: (fix_words, fix_any, slot_of_row)."""
     dev = negs.device
     n_p_rows = p_rows.shape[0]
     rp_pad = (n_p_rows + 255) // 256 * 256
@@ -814,13 +829,7 @@ def _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask):
     if p_row_mask is None:
         slot_of_row = None
     else:
-        assert p_row_mask.shape == (G, n_p_rows)
-        key = (G, n_p_rows, str(dev))
-        if key not in _ROW_IOTA:
-            ar = torch.arange(n_p_rows, dtype=torch.int32, device=dev)
-            _ROW_IOTA[key] = (ar[None].expand(G, -1).contiguous(), ar)
-        iota_g, iota = _ROW_IOTA[key]
-        row_list, _, _, n_list = token_compact(p_row_mask.contiguous(), iota_g, iota, iota, tok_cap=rp_pad)
+        row_list, n_list = _p_row_lists(p_row_mask, G, n_p_rows, rp_pad)
     if FILTER_FALSE_NEGATIVE_TEST and D >= 128:
         # prefix filter + exact pass over the survivors (same table, bit for bit); smaller dims keep the exhaustive kernel
         ws_bytes = lib.load().mhr_nce_fix_bits_filtered_workspace_bytes(n_p_rows, n_neg, G)
@@ -831,12 +840,7 @@ def _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask):
     else:
         lib.call("mhr_nce_fix_bits", p_rows.data_ptr(), _dt(p_rows), n_p_rows, negs.data_ptr(), n_neg, D, G, float(thres),
                  fix_words.data_ptr(), _ptr(row_list), _ptr(n_list), _ptr(slot_of_row), fix_any.data_ptr(), _stream())
-    return fix_words, fix_any, slot_of_row, (row_list, n_list)
-
-
-def _fix_bits_tables(p_rows, negs, n_neg, D, G, thres, p_row_mask):
-    tabs = _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask)
-    return tabs[0], tabs[1], tabs[2]
+    return fix_words, fix_any, slot_of_row
 
 
 def nce_shared_prepare_stages(q_idx, p_idx, n_tok_dev, p_rows, negs, thres, p_row_mask, want_logs, n_q_rows=None):
@@ -867,7 +871,7 @@ def _shared_prepare_stages(q_idx, p_idx, n_tok_dev, p_rows, negs, n_neg, thres, 
         prep["row_maps"] = _row_maps(q_idx, n_tok_dev, cap, row_cap)
 
     def fix_bits():                 # the real false-negative bit table, per target row
-        prep["fix"] = _fix_bits_tables(p_rows, negs, n_neg, D, G, thres, p_row_mask)
+        prep["fix"] = _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask)
 
     def rows_and_zeros():
         prep["r_p"] = torch.gather(p_idx, 1, prep["row_maps"][2].long().clamp_(max=cap - 1)).contiguous()
@@ -971,7 +975,7 @@ def _nce_fwd_shared(sv, q_rows, p_rows, negs, logit_scale, thres, want_logs, buc
 
 
 def nce_fwd(q_rows, q_idx, p_rows, p_idx, negs, n_tok_dev, tok_cap, logit_scale, thres=0.99, want_logs=False,
-            for_backward=True, bucket_idx=None, n_buckets=0, log_group=-1, p_row_mask=None, share_rows=False, window=None,
+            bucket_idx=None, n_buckets=0, log_group=-1, p_row_mask=None, share_rows=False, window=None,
             ihn_beta=0.0, prep=None):
     """Grouped sampled softmax.  q_rows/p_rows [*, D] (bf16 or f32, same dtype, shared by all groups);
     q_idx/p_idx [G, tok_cap] int32; negs [G, n_neg, D] bf16 normalised; n_tok_dev [G] int32.
@@ -1012,7 +1016,7 @@ def nce_fwd(q_rows, q_idx, p_rows, p_idx, negs, n_tok_dev, tok_cap, logit_scale,
     sv.ihn_beta = float(ihn_beta)
     sv.wide = D not in STREAM_DIMS or sv.ihn_beta > 0     # feature dims beyond the register-stationary kernels (and the IHN loss): wide.py
     sv.bucket_idx, sv.n_buckets, sv.bucket_sum, sv.bucket_cnt = bucket_idx, int(n_buckets), None, None
-    shared_path = share_rows and SHARE_ROWS and for_backward and D in STREAM_DIMS and float(ihn_beta) <= 0
+    shared_path = share_rows and SHARE_ROWS and D in STREAM_DIMS and float(ihn_beta) <= 0
     zf = zeros_many(dev, ((2, G, max(n_buckets, 1)), torch.float32), ((G, cap), torch.float32), ((G, cap), torch.float32),
                     ((G, cap) if (want_logs and not shared_path) else (1,), torch.int32),
                     ((G, cap) if (want_logs and not shared_path) else (1,), torch.int32))
@@ -1028,22 +1032,19 @@ def nce_fwd(q_rows, q_idx, p_rows, p_idx, negs, n_tok_dev, tok_cap, logit_scale,
     if sv.ihn_beta > 0:
         sv.ihn_num = torch.zeros(G, cap, dtype=torch.float32, device=dev)
         sv.ihn_imp = torch.zeros(G, cap, dtype=torch.float32, device=dev)
-    if share_rows and SHARE_ROWS and for_backward and not sv.wide:
+    if share_rows and SHARE_ROWS and not sv.wide:
         sv.negs = negs
         sv.n_tok_dev, sv.tok_cap, sv.cap, sv.thres, sv.dim, sv.n_neg, sv.groups = n_tok_dev, tok_cap, cap, float(thres), D, n_neg, G
         return _nce_fwd_shared(sv, q_rows, p_rows, negs, logit_scale, thres, want_logs, bucket_idx, n_buckets, log_group,
                                p_row_mask, loss, window, prep)
-    if for_backward or sv.wide:
-        sv.qn = torch.empty(G, cap, D, dtype=torch.bfloat16, device=dev)
-        sv.pn = torch.empty(G, cap, D, dtype=torch.bfloat16, device=dev)
-        sv.q_inv = torch.empty(G, cap, dtype=torch.float32, device=dev)
-        sv.p_inv = torch.empty(G, cap, dtype=torch.float32, device=dev)
-        sv.supp = sv.u = None
-        if not sv.wide:
-            sv.supp = torch.empty(G, (n_neg + 31) // 32, cap, dtype=torch.int32, device=dev)
-            sv.u = torch.empty(G, cap, D, dtype=torch.float32, device=dev)  # unnormalised token-side gradient (fused forward)
-    else:
-        sv.qn = sv.pn = sv.supp = sv.q_inv = sv.p_inv = sv.u = None
+    sv.qn = torch.empty(G, cap, D, dtype=torch.bfloat16, device=dev)
+    sv.pn = torch.empty(G, cap, D, dtype=torch.bfloat16, device=dev)
+    sv.q_inv = torch.empty(G, cap, dtype=torch.float32, device=dev)
+    sv.p_inv = torch.empty(G, cap, dtype=torch.float32, device=dev)
+    sv.supp = sv.u = None
+    if not sv.wide:
+        sv.supp = torch.empty(G, (n_neg + 31) // 32, cap, dtype=torch.int32, device=dev)
+        sv.u = torch.empty(G, cap, D, dtype=torch.float32, device=dev)  # unnormalised token-side gradient (fused forward)
     sv.negs = negs
     sv.n_tok_dev, sv.tok_cap, sv.cap, sv.thres, sv.dim, sv.n_neg, sv.groups = n_tok_dev, tok_cap, cap, float(thres), D, n_neg, G
     if sv.wide:
@@ -1055,27 +1056,20 @@ def nce_fwd(q_rows, q_idx, p_rows, p_idx, negs, n_tok_dev, tok_cap, logit_scale,
         return sv
     ssum = torch.zeros(G, cap, dtype=torch.float32, device=dev)
     st = _stream()
-    # training path: the false-negative test runs once per (group, target row, negative) into a bit table (see mhr.h)
+    # hoisted form (mhr.h): the false-negative test runs once per (group, target row, negative) into a bit table.  The table is
+    # the exhaustive one, built inside mhr_nce_fwd: the token kernel reads every word of it
     n_p_rows = p_rows.shape[0]
-    fix_words = None
+    rp_pad = (n_p_rows + 255) // 256 * 256
+    fix_words = torch.empty(G, (n_neg + 31) // 32, rp_pad, dtype=torch.int32, device=dev)
     row_list = n_list = slot_of_row = None
-    if sv.u is not None and HOIST_FALSE_NEGATIVE_TEST:
-        rp_pad = (n_p_rows + 255) // 256 * 256
-        fix_words = torch.empty(G, (n_neg + 31) // 32, rp_pad, dtype=torch.int32, device=dev)
-        if p_row_mask is not None:
-            assert p_row_mask.shape == (G, n_p_rows)
-            key = (G, n_p_rows, str(dev))
-            if key not in _ROW_IOTA:
-                ar = torch.arange(n_p_rows, dtype=torch.int32, device=dev)
-                _ROW_IOTA[key] = (ar[None].expand(G, -1).contiguous(), ar)
-            iota_g, iota = _ROW_IOTA[key]
-            row_list, _, _, n_list = token_compact(p_row_mask.contiguous(), iota_g, iota, iota, tok_cap=rp_pad)
-            slot_of_row = torch.zeros(G, n_p_rows, dtype=torch.int32, device=dev)     # zero: any lookup stays in bounds
+    if p_row_mask is not None:
+        row_list, n_list = _p_row_lists(p_row_mask, G, n_p_rows, rp_pad)
+        slot_of_row = torch.zeros(G, n_p_rows, dtype=torch.int32, device=dev)     # zero: any lookup stays in bounds
     _timed_call("mhr_nce_fwd", q_rows.data_ptr(), q_idx.data_ptr(), p_rows.data_ptr(), p_idx.data_ptr(), _dt(q_rows),
                 negs.data_ptr(), n_neg, D, G, n_tok_dev.data_ptr(), cap, logit_scale.data_ptr(), float(thres),
-                ssum.data_ptr(), _ptr(n_valid), _ptr(rank), _ptr(sv.qn), _ptr(sv.pn),
-                _ptr(sv.supp), _ptr(sv.q_inv), _ptr(sv.p_inv), _ptr(sv.s_pos), int(log_group), _ptr(sv.u), n_p_rows,
-                _ptr(fix_words), _ptr(row_list), _ptr(n_list), _ptr(slot_of_row), st)
+                ssum.data_ptr(), _ptr(n_valid), _ptr(rank), sv.qn.data_ptr(), sv.pn.data_ptr(),
+                sv.supp.data_ptr(), sv.q_inv.data_ptr(), sv.p_inv.data_ptr(), sv.s_pos.data_ptr(), int(log_group), sv.u.data_ptr(),
+                n_p_rows, fix_words.data_ptr(), _ptr(row_list), _ptr(n_list), _ptr(slot_of_row), st)
     lib.call("mhr_nce_finalize", ssum.data_ptr(), sv.s_pos.data_ptr(), G, n_tok_dev.data_ptr(), cap,
              logit_scale.data_ptr(), loss.data_ptr(), sv.lse.data_ptr(), _ptr(n_valid), _ptr(bucket_idx), int(n_buckets),
              _ptr(sv.bucket_sum), _ptr(sv.bucket_cnt), st)

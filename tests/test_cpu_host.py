@@ -38,6 +38,26 @@ def test_library_exports_every_declared_symbol(built_lib):
     assert rc == -1 and b"null" in dll.mhr_last_error()
     rc = dll.mhr_catalog_score_emit(1, 4, 4, 1, 100, 48, 0, 1, None, 1, 1, None, None, 1, 1, 1, 16, None)
     assert rc == -1 and b"dim=48" in dll.mhr_last_error()
+    # mhr_nce_fwd takes the hoisted and the plain form only: the removed forms are rejected by name, before any launch
+    # (the pointers are dummies that a launch would fault on)
+    P = 64
+
+    def nce_fwd(u_out, supp_out, fix_words):
+        return dll.mhr_nce_fwd(P, P, P, P, 1, P, 64, 64, 1, P, 32, P, 0.99, P, None, None, P, P, supp_out, P, P, P, -1, u_out, 8,
+                               fix_words, None, None, None, None)
+    rc = nce_fwd(None, P, P)
+    msg = dll.mhr_last_error()
+    assert rc == -1 and b"non-fused forward" in msg and b"removed" in msg
+    rc = nce_fwd(P, P, None)
+    msg = dll.mhr_last_error()
+    assert rc == -1 and b"per-token" in msg and b"removed" in msg
+
+
+def test_nce_fwd_has_no_switch_for_the_removed_forward_kernels():
+    import inspect
+    from mhr_amd import ops
+    assert "for_backward" not in inspect.signature(ops.nce_fwd).parameters
+    assert not hasattr(ops, "HOIST_FALSE_NEGATIVE_TEST")
 
 
 def test_workspace_queries(built_lib):

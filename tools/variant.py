@@ -1,10 +1,10 @@
 """Build / run an experiment variant of the HIP library (extra -D flags), without touching the product library.
 
-    python tools/variant.py build "EXP_NOSREAD EXP_NOTR"          # here: hipcc ... -DEXP_NOSREAD -DEXP_NOTR -> tools/_exp/<name>/libmhr_hip.so
-    python tools/variant.py run   "EXP_NOSREAD EXP_NOTR" tools/nce_micro.py   # on the GPU box: the script runs against that library
+    python tools/variant.py build "EXP_NOSREAD"          # here: hipcc ... -DEXP_NOSREAD -> tools/_exp/<name>/libmhr_hip.so
+    python tools/variant.py run   "EXP_NOSREAD" tools/nce_micro.py   # on the GPU box: the script runs against that library
 
-The EXP_* timing experiments (garbage-value paths that REMOVE a piece of the tile step: no LDS reads, no transposed reads,
-no waits) are not in the product sources: `tools/exp_variants.patch` adds them to a scratch copy of csrc/ that this script
+The EXP_* timing experiments (garbage-value paths that REMOVE a piece of a tile loop: EXP_NOSREAD, no row-fragment LDS reads
+in sg::mma_tile) are not in the product sources: `tools/exp_variants.patch` adds them to a scratch copy of csrc/ that this script
 builds from whenever a requested define starts with EXP_.
 """
 import glob
