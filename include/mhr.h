@@ -248,6 +248,16 @@ int mhr_rows_gemm_supported(int M, int N, int K, int w_is_kn);
 int mhr_rows_gemm(const void* a, int64_t lda, const void* w, int64_t ldw, int w_is_kn, const void* bias,
                   void* c, int64_t ldc, int M, int N, int K, void* stream);
 
+/* The same product without bias for the deep contraction K = 1024: the input gradients of the uvqk projection
+ * (dx = dh . W_uvqk^T, W stored [N,K] = [256,1024]: w_is_kn = 0) and of the decoding heads (dx = dz . W_heads, W stored
+ * [K,N] = [1024,256]: w_is_kn = 1).  K = 1024, N a multiple of 128, any M >= 1; lda / ldc may exceed the row (column blocks
+ * of wider buffers); leading dimensions multiples of 8 elements, 16-byte aligned operands.  One fixed summation order per
+ * output element (no atomics, no split-K partials): two calls are bitwise equal.  mhr_rows_gemm_deep_supported answers
+ * whether a shape is covered; the caller uses the library GEMM otherwise. */
+int mhr_rows_gemm_deep_supported(int M, int N, int K, int w_is_kn);
+int mhr_rows_gemm_deep(const void* a, int64_t lda, const void* w, int64_t ldw, int w_is_kn,
+                       void* c, int64_t ldc, int M, int N, int K, void* stream);
+
 /* Sequence layout of a batch of masks, computed once per batch and shared by every layer's attention launches:
  * first_block[b] = the 32-row block holding sequence b's first valid key (ceil(L/32) when it has none); seq_order (optional) =
  * the sequences sorted by it, most live blocks first (stable).  The reference's loaders pad at the FRONT (data/dataset/

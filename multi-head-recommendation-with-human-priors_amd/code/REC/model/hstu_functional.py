@@ -172,6 +172,31 @@ def _rows_gemm_pays(x, w_kn):
             and ops.rows_gemm_supported(M, N, K, True))
 
 
+ROWS_GEMM_DEEP = os.environ.get("MHR_ROWS_GEMM_DEEP", "1") != "0"
+# Routed where it was faster than the library product in three of three repeats (tools/rows_gemm_micro.py):
+# at the packed capacities 16 384 and 18 432; at 25 600 rows the library is level or ahead, so the window is closed above.
+ROWS_GEMM_DEEP_MIN_M = int(os.environ.get("MHR_ROWS_GEMM_DEEP_MIN_M", "16384"))
+ROWS_GEMM_DEEP_MAX_M = int(os.environ.get("MHR_ROWS_GEMM_DEEP_MAX_M", "18432"))
+
+
+def _rows_gemm_deep_pays(dy, w, w_is_kn):
+    """The K = 1024 input gradients (ops.rows_gemm_deep): dx = dy @ w.T (w [N, 1024]) or dy @ w (w_is_kn, w [1024, N]) with
+    enough token rows to amortise the 256 KiB of stationary operand every workgroup loads, and not so many that the library's
+    larger tiles catch up."""
+    M, K = dy.shape
+    N = w.shape[1] if w_is_kn else w.shape[0]
+    return (ROWS_GEMM_DEEP and ROWS_GEMM_DEEP_MIN_M <= M <= ROWS_GEMM_DEEP_MAX_M and dy.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+            and dy.is_contiguous() and w.dim() == 2 and w.stride(1) == 1 and w.stride(0) % 8 == 0
+            and dy.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0 and ops.rows_gemm_deep_supported(M, N, K, w_is_kn))
+
+
+def _input_grad(dy, w, w_is_kn):
+    """dx of a dense projection: dy @ w (w_is_kn) or dy @ w.T."""
+    if _rows_gemm_deep_pays(dy, w, w_is_kn):
+        return ops.rows_gemm_deep(dy, w, w_is_kn=w_is_kn)
+    return dy @ w if w_is_kn else dy @ w.t()
+
+
 class SplitKLinearFn(Function):
     """y = x @ W (w_is_nk=False, W [K, N]) or x @ W.T + b (w_is_nk=True, W [N, K], the nn.Linear layout), bf16 GEMMs on
     fp32 master weights (reference hstu.py:236-239 under bf16-mixed autocast).
@@ -218,7 +243,7 @@ class SplitKLinearFn(Function):
     def backward(ctx, dy):
         x, wb = ctx.saved_tensors
         dy = dy.contiguous()
-        dx = dy @ wb if ctx.w_is_nk else dy @ wb.t()
+        dx = _input_grad(dy, wb, ctx.w_is_nk)     # (the uvqk layer's [M, 1024] x [1024, 256]: the hand-written deep product)
         R = x.shape[0]
         if ctx.defer is not None and ctx.w_leaf is not None:
             stack, kind, layer = ctx.defer
@@ -277,7 +302,7 @@ class FusedHeadsLinearFn(Function):
     def backward(ctx, dy):
         x, w16 = ctx.saved_tensors
         dy = dy.contiguous()
-        dx = dy @ w16
+        dx = _input_grad(dy, w16, True)
         R = x.shape[0]
         tiles = -(-w16.shape[0] // 256) * -(-w16.shape[1] // 256)
         s_max = min(max(1, 256 // tiles), _SPLITK_MAX)

@@ -284,6 +284,183 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(const bf16_t* __restr
   RG_STAMP(3)
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The deep form, K = 1024: the input gradients of the uvqk projection (dx = dh . W_uvqk^T, W stored [256, 1024]) and of the
+// decoding heads (dx = dz . W_heads, W stored [1024, 256]).  One wave per SIMD; a wave owns 32 output columns over the whole
+// K: 64 k-step fragments = 256 registers of stationary W and ONE accumulator.  The token rows stream in K-chunks of 256 -
+// sg::Tile<16> images of 16 KiB fetched with a source row stride - through a 4-slot ring, so the chunk index, and with it the
+// fragment block, is the compile-time ring slot; three chunks are in flight while one is consumed.  The accumulator is carried
+// over a row tile's four chunks, the epilogue (rows_gemm_kernel's, one fragment) runs after the fourth and the tile's two
+// stores ride the gaps of the next tile's first chunk.
+//
+// The stationary load moves 256 KiB per workgroup and is bound by what is in flight.  W [N, K]: each wave fetches ITS 32 rows in
+// sixteen images of 64 k (sg::Tile<4>, 4 KiB) through six wave-private buffers - no barrier: a counted vmcnt wait, four row
+// reads, and the buffer is refilled with the round six ahead, so five rounds (80 KiB per CU) are always in flight.  W [K, N]:
+// 32-row k tiles x the group's 128 columns, eight per round shared by the four waves, fragments by the transposing read as in
+// rows_gemm_kernel.  The first three row chunks' DMA is issued before either, so their HBM latency passes under the load.
+template <bool W_KN, bool PARTIAL>
+__global__ __launch_bounds__(256, 1) void rows_gemm_deep_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restrict__ W,
+                                                                int64_t ldw, bf16_t* __restrict__ C, int64_t ldc, int M, int n_tiles,
+                                                                int n_cg, int n_streams) {
+  using T = sg::Tile<16>;                                   // a streamed chunk: 32 token rows x 256 k
+  using TW = sg::Tile<8>;                                   // a staging image of W
+  constexpr int NC = 4;                                     // chunks per row tile = ring slots
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char* ring = smem;                               // NC x T::BYTES
+  unsigned char* stg = smem + NC * T::BYTES;                // 80 KiB: 4 waves x 5 images of 4 KiB ([N, K]) / 8 x TW::BYTES ([K, N])
+
+  const int w = blockIdx.x, xcd = w & 7, j = w >> 3;        // XCD-aware decode (the column groups of a stream share an L2)
+  const int cg = j % n_cg, stream = (j / n_cg) * 8 + xcd;
+  const int t0 = (int)((int64_t)stream * n_tiles / n_streams), t1 = (int)((int64_t)(stream + 1) * n_tiles / n_streams);
+  if (t0 >= t1) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, half = lane >> 5;
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  const int n_wave = cg * 128 + wv * 32;                    // first output column of this wave
+  const int t_last = t1 - 1;
+
+  using P = sg::DmaPieces<16>;
+  P dp;
+  dp.init(wv, lane, (int)(lda * 2));
+  auto dma_piece = [&](auto slot_c, auto k_c, int tn) {     // piece k of chunk `slot` of row tile tn into ring slot `slot`
+    constexpr int slot = decltype(slot_c)::value, k = decltype(k_c)::value;
+    if constexpr (PARTIAL) {
+      dp.template piece_rows<k>(ring + slot * T::BYTES, [=](int rr) {
+        const int m = tn * 32 + rr;
+        return A + (int64_t)(m < M ? m : M - 1) * lda + slot * 256;
+      }, lane);
+    } else {
+      dp.template piece<k>(ring + slot * T::BYTES, reinterpret_cast<const char*>(A + (int64_t)tn * 32 * lda + slot * 256));
+    }
+  };
+  auto dma_chunk = [&](auto slot_c, int tn) {
+    auto f = [&](auto k_c) { dma_piece(slot_c, k_c, tn); };
+    sg::static_for<P::PW>(f);
+  };
+  dma_chunk(std::integral_constant<int, 0>{}, t0);
+  dma_chunk(std::integral_constant<int, 1>{}, t0);
+  dma_chunk(std::integral_constant<int, 2>{}, t0);
+
+  bf16x8 frag[NC][1][16];
+  if constexpr (!W_KN) {
+    using TQ = sg::Tile<4>;                                   // a wave-private image: this wave's 32 rows of W x 64 k, 4 KiB
+    constexpr int NB = 6, NR = 16;                            // images per wave (the sixth in the ring's idle fourth slot), rounds
+    sg::LaneAddr<4> lw;
+    lw.init(lane);
+    unsigned char* my = stg + wv * 5 * TQ::BYTES;
+    unsigned char* my5 = ring + 3 * T::BYTES + wv * TQ::BYTES;
+    const uint32_t my_addr = sg::lds_addr(my), my5_addr = sg::lds_addr(my5);
+    const int slot = lane & 7;                                // (a 1-KiB piece = 8 rows of 8 slots)
+    const bf16_t* wrow = W + (int64_t)(n_wave + (lane >> 3)) * ldw;
+    auto w_issue = [&](auto rd_c) {
+      constexpr int rd = decltype(rd_c)::value, b = rd % NB;
+      unsigned char* img = b < 5 ? my + b * TQ::BYTES : my5;
+#pragma unroll
+      for (int pc = 0; pc < 4; ++pc) {
+        const int row = pc * 8 + (lane >> 3);
+        const bf16_t* src = wrow + (int64_t)(pc * 8) * ldw + rd * 64 + ((slot ^ TQ::key(row)) << 3);
+        __builtin_amdgcn_global_load_lds((sg::gptr_t)src, (sg::lptr_t)(img + pc * 1024), 16, 0, 0);
+      }
+    };
+    sg::static_for<NB>(w_issue);
+    auto w_round = [&](auto rd_c) {
+      constexpr int rd = decltype(rd_c)::value, b = rd % NB;
+      constexpr int younger = (NR - 1 - rd) < NB - 1 ? (NR - 1 - rd) : NB - 1;   // rounds in flight behind this one
+      sg::wait_vmcnt<4 * younger>();                          // round rd has landed (and the row chunks issued before it)
+      const uint32_t base = b < 5 ? my_addr + b * TQ::BYTES : my5_addr;
+      sg::u32x4 v[4];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) v[ks] = sg::ds_read_b128_asm<0>(base + (uint32_t)lw.a[ks]);
+      sg::wait_lgkm_values<0>(v[0], v[1], v[2], v[3]);
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) frag[rd >> 2][0][(rd & 3) * 4 + ks] = __builtin_bit_cast(bf16x8, v[ks]);
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (rd + NB < NR) w_issue(std::integral_constant<int, rd + NB>{});
+    };
+    sg::static_for<NR>(w_round);
+  } else {
+    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+    sg::LaneAddr<8> lw;
+    lw.init(lane);
+    // this wave's 32-column block of a tile: dc = wv (selected, not indexed: a runtime index would put the array in scratch)
+    const int tr0 = wv == 0 ? lw.t[0][0] : wv == 1 ? lw.t[0][1] : wv == 2 ? lw.t[0][2] : lw.t[0][3];
+    const int tr1 = wv == 0 ? lw.t[1][0] : wv == 1 ? lw.t[1][1] : wv == 2 ? lw.t[1][2] : lw.t[1][3];
+#pragma unroll
+    for (int rd = 0; rd < 4; ++rd) {                          // eight 32-row k tiles per round: k-chunk rd
+      if (rd) __syncthreads();                                // every wave has read its fragments of the previous round
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int k0 = (rd * 8 + q) * 32;
+        sg::Dma<8>::issue(stg + q * TW::BYTES, [=](int rr) { return W + (int64_t)(k0 + rr) * ldw + cg * 128; }, wv, lane);
+      }
+      sg::wait_vmcnt<0>();
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          const unsigned char* base = stg + q * TW::BYTES + 16 * s2 * TW::ROW_BYTES;
+          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base + tr0));
+          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base + tr1));
+          const u32x2_t l2 = __builtin_bit_cast(u32x2_t, lo), h2 = __builtin_bit_cast(u32x2_t, hi);
+          const u32x2_t s0 = __builtin_amdgcn_permlane32_swap(l2.x, h2.x, false, false);
+          const u32x2_t s1 = __builtin_amdgcn_permlane32_swap(l2.y, h2.y, false, false);
+          frag[rd][0][q * 2 + s2] = __builtin_bit_cast(bf16x8, sg::u32x4{s0.x, s1.x, s0.y, s1.y});
+        }
+      }
+    }
+  }
+
+  sg::LaneAddr<16> la;
+  la.init(lane);
+  sg::RowAddr<16> ra;
+  ra.init(la, ring);
+  const int n_lane = n_wave + 8 * half;                       // after the exchange lane (r, half) holds columns n_lane + 16 gp + 0..7
+  sg::u32x4 o[2];
+  auto store_piece = [&](auto gp_c, int ts, bool all) {
+    constexpr int gp = decltype(gp_c)::value;
+    bf16_t* p = C + (int64_t)(ts * 32 + r) * ldc + n_lane + gp * 16;
+    if (all || ts * 32 + r < M) *reinterpret_cast<sg::u32x4*>(p) = o[gp];
+  };
+  f32x16 acc[1];
+  acc[0] = sg::zero16();
+  sg::ring_loop<NC>(NC * (t1 - t0), [&](auto slot_c, int i) {
+    constexpr int cur = decltype(slot_c)::value, nxt = (cur + 3) % NC;
+    const int t = t0 + (i >> 2);
+    // The wait counts the LDS-DMA pieces younger than this chunk's last piece: those issued in the two units since.  The
+    // previous tile's two stores, where one of those units was a chunk 0, are left out of the count: it is then smaller than
+    // the truth, never larger, and the wait does not depend on how stores retire relative to loads.
+    sg::wait_vmcnt<2 * P::PW>();
+    sg::ring_barrier();
+    if constexpr (cur == 0) acc[0] = sg::zero16();
+    const int t_dma = min(t + (cur >= 1 ? 1 : 0), t_last);    // unit i + 3 (past the end: the last tile again, never read)
+    mma_tile_gaps<16, 1, cur * T::BYTES>(ra, frag[cur], acc, [&](auto ks_c) {
+      constexpr int ks = decltype(ks_c)::value;
+      if constexpr (ks % 4 == 0) dma_piece(std::integral_constant<int, nxt>{}, std::integral_constant<int, ks / 4>{}, t_dma);
+      if constexpr (cur == 0 && (ks == 2 || ks == 6)) {
+        if (i > 0) store_piece(std::integral_constant<int, (ks - 2) / 4>{}, t - 1, true);   // (tile t - 1 is never the partial last tile)
+      }
+    });
+    if constexpr (cur == NC - 1) {
+#pragma unroll
+      for (int gp = 0; gp < 2; ++gp) {                        // column groups G = 2 gp (x) and 2 gp + 1 (y)
+        const int gx = 8 * gp, gy = 8 * gp + 4;
+        const uint32_t x0 = sg::cvt_pk_bf16(acc[0][gx + 0], acc[0][gx + 1]), x1 = sg::cvt_pk_bf16(acc[0][gx + 2], acc[0][gx + 3]);
+        const uint32_t y0 = sg::cvt_pk_bf16(acc[0][gy + 0], acc[0][gy + 1]), y1 = sg::cvt_pk_bf16(acc[0][gy + 2], acc[0][gy + 3]);
+        const u32x2_t s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
+        const u32x2_t s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
+        o[gp] = sg::u32x4{s0.x, s1.x, s0.y, s1.y};
+      }
+    }
+  });
+  {                                                           // the last tile's stores
+    const bool all = t_last * 32 + 32 <= M;
+    auto st = [&](auto gp_c) { store_piece(gp_c, t_last, all); };
+    sg::static_for<2>(st);
+  }
+  sg::wait_vmcnt<0>();
+}
+
 }  // namespace
 
 #ifdef RGX_STAMP
@@ -335,5 +512,44 @@ extern "C" int mhr_rows_gemm(const void* a, int64_t lda, const void* w, int64_t 
 #undef L___
 #undef L____
   MHR_CHECK_LAUNCH("rows_gemm");
+  return MHR_OK;
+}
+
+extern "C" int mhr_rows_gemm_deep_supported(int M, int N, int K, int w_is_kn) {
+  (void)w_is_kn;                                           // both weight layouts
+  return K == 1024 && N > 0 && N % 128 == 0 && M > 0;
+}
+
+extern "C" int mhr_rows_gemm_deep(const void* a, int64_t lda, const void* w, int64_t ldw, int w_is_kn, void* c, int64_t ldc, int M,
+                                  int N, int K, void* stream) {
+  MHR_REQUIRE(a && w && c, "rows_gemm_deep: null pointer");
+  MHR_REQUIRE(mhr_rows_gemm_deep_supported(M, N, K, w_is_kn),
+              "rows_gemm_deep: M=%d N=%d K=%d unsupported (K = 1024; N a multiple of 128)", M, N, K);
+  MHR_REQUIRE(lda >= K && ldw >= (w_is_kn ? N : K) && ldc >= N && lda % 8 == 0 && ldw % 8 == 0 && ldc % 8 == 0 && lda <= (1 << 24),
+              "rows_gemm_deep: leading dimensions must cover the rows and be multiples of 8 elements (lda at most 2^24)");
+  MHR_REQUIRE(((uintptr_t)a | (uintptr_t)w | (uintptr_t)c) % 16 == 0, "rows_gemm_deep: operands must be 16-byte aligned");
+  const int n_tiles = (M + 31) / 32;
+  const int n_cg = N / 128;
+  // one workgroup per CU; every stream needs a few tiles to amortise the 256 KiB of stationary operand per workgroup
+  int n_streams = (256 / n_cg) & ~7;
+  while (n_streams > 8 && n_tiles / n_streams < 2) n_streams -= 8;
+  if (n_streams < 8) n_streams = 8;
+  const bool partial = M % 32 != 0;
+  const size_t lds = 4 * (size_t)16384 + 20 * (size_t)4096;  // the ring of row chunks + the staging images of W
+  hipStream_t s = (hipStream_t)stream;
+#define L_(KN, PT)                                                                                                            \
+  {                                                                                                                           \
+    auto kern = rows_gemm_deep_kernel<KN, PT>;                                                                                \
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
+    hipLaunchKernelGGL(kern, dim3(n_cg * n_streams), dim3(256), lds, s, (const bf16_t*)a, lda, (const bf16_t*)w, ldw,          \
+                       (bf16_t*)c, ldc, M, n_tiles, n_cg, n_streams);                                                         \
+  }
+  if (w_is_kn) {
+    if (partial) L_(true, true) else L_(true, false)
+  } else {
+    if (partial) L_(false, true) else L_(false, false)
+  }
+#undef L_
+  MHR_CHECK_LAUNCH("rows_gemm_deep");
   return MHR_OK;
 }

@@ -446,6 +446,30 @@ def rows_gemm(a, w, bias=None, out=None, w_is_kn=False):
     return out
 
 
+def rows_gemm_deep_supported(M, N, K, w_is_kn=False):
+    return K == 1024 and N > 0 and N % 128 == 0 and M > 0                                        # (= mhr_rows_gemm_deep_supported)
+
+
+def rows_gemm_deep(a, w, out=None, w_is_kn=False):
+    """out [M, N] bf16 = a [M, 1024] @ w.T (w [N, 1024]; w_is_kn: a @ w with w [1024, N]): the input gradients of the uvqk
+    projection and of the decoding heads (the autograd of hstu.py:236-239 and of llm_heads.py's linears under bf16 autocast),
+    with the whole K = 1024 of a wave's 32 output columns stationary in registers and the token rows streaming through LDS."""
+    for t_, nm in ((a, "a"), (w, "w")):                       # (rows may be a column block of a wider buffer: row strides are passed on)
+        if not (t_.is_cuda and t_.dtype == torch.bfloat16 and t_.dim() == 2 and t_.stride(1) == 1):
+            raise ValueError(f"rows_gemm_deep: {nm} must be a 2-d bf16 device tensor with unit inner stride")
+    M, K = a.shape
+    N = w.shape[1] if w_is_kn else w.shape[0]
+    if (w.shape[0] if w_is_kn else w.shape[1]) != K:
+        raise ValueError("rows_gemm_deep: inner dimensions differ")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
+    elif out.shape != (M, N) or out.dtype != torch.bfloat16 or out.stride(1) != 1:
+        raise ValueError("rows_gemm_deep: out must be [M, N] bf16 with unit inner stride")
+    _timed_call("mhr_rows_gemm_deep", a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), 1 if w_is_kn else 0,
+                out.data_ptr(), out.stride(0), M, N, K, _stream())
+    return out
+
+
 def seq_pack_maps(key_valid, B, L, capacity, guard=None):
     """(cu_rows [B+1], src_of [capacity], row_of [B*L], overflow [1]) int32 of a batch of masks (mhr_seq_pack_maps).
     guard (int32 [4] device tensor of the caller, zeroed once): the same maps through mhr_seq_pack_maps_guarded, which also
