@@ -733,15 +733,13 @@ class NceLossFn(Function):
         q_idx, p_idx, logit_scale = ctx.saved_tensors
         sv = ctx.sv
         q_shape, p_shape = ctx.shapes
-        bufs, sv.bwd_bufs = getattr(sv, "bwd_bufs", None), None
-        d_negs0 = d_ls0 = lw_row = None
-        if bufs is not None and bufs[0].shape == q_shape and bufs[1].shape == p_shape:     # zeroed early (ops.nce_shared_prepare)
-            dq, dp, d_negs0, d_ls0, lw_row = bufs
-            if not ctx.needs_input_grad[2]:
-                d_negs0 = None
-        else:
-            dq = torch.zeros(q_shape, dtype=torch.float32, device=d_out.device)
-            dp = torch.zeros(p_shape, dtype=torch.float32, device=d_out.device)
+        bufs = sv.take_bwd_bufs() if sv.shared else None      # the accumulators ops.nce_shared_prepare zeroed early, if it did
+        if bufs is None or bufs[0].shape != q_shape or bufs[1].shape != p_shape:
+            bufs = (torch.zeros(q_shape, dtype=torch.float32, device=d_out.device),
+                    torch.zeros(p_shape, dtype=torch.float32, device=d_out.device), None, None, None)
+        dq, dp, d_negs0, d_ls0, lw_row = bufs
+        if not ctx.needs_input_grad[2]:
+            d_negs0 = None
         if ctx.bucket_weight is not None:
             w = ops.loss_reduce_bwd(d_out, sv.bucket_cnt, ctx.bucket_weight)      # d(total)/d(loss_t) = weight / count of the bucket
         else:

@@ -5,6 +5,7 @@ PyTorch is plumbing here: device memory (`Tensor.data_ptr()`), the current HIP s
 current stream; none of them synchronises, and none has a CPU or eager fallback.
 """
 import os
+import types
 
 import torch
 
@@ -767,31 +768,61 @@ def nce_log_counters(n_valid, rank, o_idx, n_tok_dev, group, ks):
 
 
 _COUNTER_SCRATCH = {}
-
-
 STREAM_DIMS = (16, 32, 64, 128, 256)      # feature dims of the register-stationary streaming kernels
-
-
 FILTER_FALSE_NEGATIVE_TEST = os.environ.get("MHR_NCE_FIX_FILTER", "1") != "0"    # 0: the exhaustive bit-table kernel
+SHARE_ROWS = os.environ.get("MHR_NCE_SHARE_ROWS", "1") != "0"
+DETERMINISTIC = False
+_ROW_IOTA = {}
+_ZERO_FIX = {}
+
+
+def nce_path(dim, share_rows, ihn_beta=0.0):
+    """The path a sampled-softmax call takes: "wide" (wide.py) for feature dims beyond the register-stationary kernels and for the
+    IHN loss at every dim; "shared" (query-row sharing) where the caller asks for it and SHARE_ROWS allows it; else "tokens"."""
+    if dim not in STREAM_DIMS or float(ihn_beta) > 0:
+        return "wide"
+    return "shared" if share_rows and SHARE_ROWS else "tokens"
 
 
 class NceSaved:
-    """Tensors the forward keeps for the backward (all preallocated at token capacity)."""
-    __slots__ = ("qn", "pn", "supp", "q_inv", "p_inv", "s_pos", "lse", "loss", "n_valid", "rank", "negs",
-                 "n_tok_dev", "tok_cap", "cap", "thres", "dim", "n_neg", "groups", "q_idx", "p_idx", "bucket_idx", "n_buckets",
-                 "bucket_sum", "bucket_cnt", "u", "wide", "scale_dev", "cap_eff", "wide_pack",
-                 # query-row sharing (nce_shared.hip): row-level state of the streaming kernels + the maps between rows and tokens
-                 "shared", "tok2row", "row_first", "n_row_dev", "row_cap", "fix_words", "fix_slot", "fix_any", "n_p_rows", "row_q",
-                 "window", "bwd_bufs",
-                 # REMI's interest-aware hard-negative loss (dense path): beta and the two saved log-sums per token
-                 "ihn_beta", "ihn_num", "ihn_imp")
+    """What the sampled-softmax forward keeps for the backward: here the fields every path has ([G, cap] tensors at token
+    capacity), one subclass per path (nce_path) for the rest.  Every field is given once, to the constructor."""
+    __slots__ = ("q_idx", "p_idx", "n_tok_dev", "tok_cap", "cap", "groups", "dim", "n_neg", "thres", "negs",
+                 "loss", "lse", "s_pos", "n_valid", "rank", "bucket_idx", "n_buckets", "bucket_sum", "bucket_cnt")
+    shared = wide = False
+
+    def __init__(self, loss, n_valid, rank, **fields):
+        tc = fields["tok_cap"]              # loss / n_valid / rank arrive as the [G, cap] buffers the kernels wrote: cut here, once
+        fields.update((k, None if t is None else t[:, :tc]) for k, t in (("loss", loss), ("n_valid", n_valid), ("rank", rank)))
+        names = {n for c in type(self).__mro__ for n in getattr(c, "__slots__", ())}
+        assert names == set(fields), (type(self).__name__, sorted(names ^ set(fields)))
+        for n, v in fields.items():
+            setattr(self, n, v)
 
 
-_ROW_IOTA = {}
+class NceSavedTokens(NceSaved):
+    """Per-token streaming kernels (csrc/nce.hip): everything [G, cap, ...]; u: the unnormalised token-side gradient."""
+    __slots__ = ("qn", "pn", "q_inv", "p_inv", "u", "supp")
 
 
-SHARE_ROWS = os.environ.get("MHR_NCE_SHARE_ROWS", "1") != "0"
-DETERMINISTIC = False
+class NceSavedShared(NceSaved):
+    """Query-row sharing (csrc/nce_shared.hip): row-level state of the streaming kernels + the maps between rows and tokens."""
+    __slots__ = ("qn", "u", "q_inv", "supp", "pn", "p_inv",   # per distinct query ROW (supp: None for whole-tile pools) / TARGET row
+                 "tok2row", "row_first", "row_q", "n_row_dev", "row_cap", "fix_words", "fix_slot", "fix_any", "n_p_rows",
+                 "window",                                # (tok_of_slot [G, n_slots], L, P) of window-structured lists, or None
+                 "bwd_bufs")                              # (dq, dp, d_negs, d_scale, lw_row) zeroed by an early prep, or None
+    shared = True
+
+    def take_bwd_bufs(self):                              # one backward may accumulate into them
+        bufs, self.bwd_bufs = self.bwd_bufs, None
+        return bufs
+
+
+class NceSavedWide(NceSaved):
+    """Wide / dense path (wide.py): qn .. p_inv per token; wide_pack: per group the packed negatives + suppression bits of the
+    hand-written contraction (None: dense chunks); REMI's interest-aware hard-negative loss: beta and the two saved log-sums per token."""
+    __slots__ = ("qn", "pn", "q_inv", "p_inv", "scale_dev", "cap_eff", "wide_pack", "ihn_beta", "ihn_num", "ihn_imp")
+    wide = True
 
 
 def set_deterministic(on):
@@ -809,7 +840,6 @@ if os.environ.get("MHR_DETERMINISTIC", "0") == "1":
         set_deterministic(True)
     except RuntimeError:          # (library not built yet: lib.load() raises at the first real use anyway)
         DETERMINISTIC = True
-_ZERO_FIX = {}
 
 
 def _row_maps(q_idx, n_tok_dev, cap, row_cap):
@@ -826,10 +856,17 @@ def _row_maps(q_idx, n_tok_dev, cap, row_cap):
     return r_q, tok2row, r_first, n_row
 
 
-def _p_row_lists(p_row_mask, G, n_p_rows, rp_pad):
-    """p_row_mask [G, n_p_rows] -> (row_list [G, rp_pad], n_list [G]): per group the rows of p_rows the mask names, compacted on
-    the device.  The bit-table kernels test only those rows (slot j of the list = column j of the table) and write the inverse
-    map, slot_of_row, themselves."""
+def _fix_table_geometry(p_rows, n_neg):
+    """(n_p_rows, rp_pad, n_tiles) of the bit table [G, n_tiles, rp_pad]: a column per target row (256-row blocks), a word per 32 negatives."""
+    return p_rows.shape[0], (p_rows.shape[0] + 255) // 256 * 256, (n_neg + 31) // 32
+
+
+def _p_row_lists(p_row_mask, G, n_p_rows, rp_pad, slot_of_row=None):
+    """p_row_mask [G, n_p_rows] -> (row_list [G, rp_pad], n_list [G], slot_of_row [G, n_p_rows]), all None without a mask: per group
+    the rows of p_rows the mask names, compacted on the device.  The bit-table kernels test only those rows (slot j of the list = column
+    j of the table) and write the inverse map themselves, into slot_of_row: the caller's or a new one (zero: any lookup stays in bounds)."""
+    if p_row_mask is None:
+        return None, None, None
     assert p_row_mask.shape == (G, n_p_rows)
     dev = p_row_mask.device
     key = (G, n_p_rows, str(dev))
@@ -838,22 +875,16 @@ def _p_row_lists(p_row_mask, G, n_p_rows, rp_pad):
         _ROW_IOTA[key] = (ar[None].expand(G, -1).contiguous(), ar)
     iota_g, iota = _ROW_IOTA[key]
     row_list, _, _, n_list = token_compact(p_row_mask.contiguous(), iota_g, iota, iota, tok_cap=rp_pad)
-    return row_list, n_list
+    return row_list, n_list, torch.zeros(G, n_p_rows, dtype=torch.int32, device=dev) if slot_of_row is None else slot_of_row
 
 
 def _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask):
     """The false-negative bit table of the target rows, for the row-sharing path: (fix_words, fix_any, slot_of_row)."""
     dev = negs.device
-    n_p_rows = p_rows.shape[0]
-    rp_pad = (n_p_rows + 255) // 256 * 256
-    n_tiles = (n_neg + 31) // 32
+    n_p_rows, rp_pad, n_tiles = _fix_table_geometry(p_rows, n_neg)
     fix_words = torch.empty(G, n_tiles, rp_pad, dtype=torch.int32, device=dev)
     fix_any, slot_of_row = zeros_many(dev, ((G, rp_pad), torch.int32), ((G, n_p_rows), torch.int32))
-    row_list = n_list = None
-    if p_row_mask is None:
-        slot_of_row = None
-    else:
-        row_list, n_list = _p_row_lists(p_row_mask, G, n_p_rows, rp_pad)
+    row_list, n_list, slot_of_row = _p_row_lists(p_row_mask, G, n_p_rows, rp_pad, slot_of_row)
     if FILTER_FALSE_NEGATIVE_TEST and D >= 128:
         # prefix filter + exact pass over the survivors (same table, bit for bit); smaller dims keep the exhaustive kernel
         ws_bytes = lib.load().mhr_nce_fix_bits_filtered_workspace_bytes(n_p_rows, n_neg, G)
@@ -867,48 +898,60 @@ def _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask):
     return fix_words, fix_any, slot_of_row
 
 
+class NcePrep:
+    """The batch-only half of the row-sharing forward; the stages of `nce_shared_prepare_stages` fill it in order."""
+    __slots__ = ("key", "keep",                                        # _prep_key of the call it serves; those inputs, kept alive
+                 "row_q", "tok2row", "row_first", "n_row", "r_p",     # _row_maps of the lists; the target of every row's first token
+                 "fix_words", "fix_any", "slot_of_row",               # _fix_bits_launch: the bit table of the target rows
+                 "sum_row", "nv_row", "rk_row", "n_valid", "rank",    # zeroed: per row / per token (counters: None without logs)
+                 "pn_rows", "p_inv", "bwd")       # normalised target rows; (dq, dp, d_negs, d_scale, lw_row) with n_q_rows, else None
+
+
+def _prep_key(q_idx, p_idx, p_rows, negs, thres, want_logs):
+    return (q_idx.data_ptr(), p_idx.data_ptr(), p_rows.data_ptr(), negs.data_ptr(), float(thres), bool(want_logs))
+
+
 def nce_shared_prepare_stages(q_idx, p_idx, n_tok_dev, p_rows, negs, thres, p_row_mask, want_logs, n_q_rows=None):
     """Everything the row-sharing forward needs that depends on the BATCH only (token lists, target rows, negatives) and not
     on the query rows: the row maps of the token lists, the false-negative bit table of the target rows, the first target of
     every row, the normalised target rows and the zeroed accumulators (with n_q_rows, the number of query rows, the backward's
     accumulators as well).  `nce_fwd(share_rows=True)` builds it itself; a model may build it EARLY - on a second stream
     underneath the sequence encoder, a stage at a time between the encoder's layers - and hand it in (`prep=`).
-    Returns (prep, stages): the dict the stages fill, and the stages (callables, to be run in order on one stream); (None, [])
+    Returns (prep, stages): the NcePrep the stages fill, and the stages (callables, to be run in order on one stream); (None, [])
     when the shapes are not the row-sharing path's (ragged capacity / pool sizes, feature dims it does not take)."""
-    G, cap = q_idx.shape
-    n_neg, D = negs.shape[1], negs.shape[2]
-    if not SHARE_ROWS or D not in STREAM_DIMS or cap % 32 or n_neg % 32:
+    cap, n_neg, D = q_idx.shape[1], negs.shape[1], negs.shape[2]
+    # whole tiles only: nce_fwd pads a ragged capacity or pool into NEW tensors, which an early prep cannot have been built for
+    if nce_path(D, True) != "shared" or cap % 32 or n_neg % 32:
         return None, []
     return _shared_prepare_stages(q_idx, p_idx, n_tok_dev, p_rows, negs, n_neg, thres, p_row_mask, want_logs, n_q_rows)
 
 
 def _shared_prepare_stages(q_idx, p_idx, n_tok_dev, p_rows, negs, n_neg, thres, p_row_mask, want_logs, n_q_rows=None):
     """(n_neg: the pool's own size; `negs` may be padded to whole 32-row tiles behind it)"""
-    G, cap = q_idx.shape
-    D = negs.shape[2]
-    dev = negs.device
+    (G, cap), D, dev = q_idx.shape, negs.shape[2], negs.device
     row_cap = cap + 32
-    prep = {"key": (q_idx.data_ptr(), p_idx.data_ptr(), p_rows.data_ptr(), negs.data_ptr(), float(thres), bool(want_logs)),
-            "keep": (q_idx, p_idx, p_rows, negs)}
+    prep = NcePrep()
+    prep.key, prep.keep, prep.bwd = _prep_key(q_idx, p_idx, p_rows, negs, thres, want_logs), (q_idx, p_idx, p_rows, negs), None
 
     def row_maps():
-        prep["row_maps"] = _row_maps(q_idx, n_tok_dev, cap, row_cap)
+        prep.row_q, prep.tok2row, prep.row_first, prep.n_row = _row_maps(q_idx, n_tok_dev, cap, row_cap)
 
     def fix_bits():                 # the real false-negative bit table, per target row
-        prep["fix"] = _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask)
+        prep.fix_words, prep.fix_any, prep.slot_of_row = _fix_bits_launch(p_rows, negs, n_neg, D, G, thres, p_row_mask)
 
     def rows_and_zeros():
-        prep["r_p"] = torch.gather(p_idx, 1, prep["row_maps"][2].long().clamp_(max=cap - 1)).contiguous()
-        prep["z"] = zeros_many(dev, ((G, row_cap), torch.float32), ((G, row_cap), torch.int32), ((G, row_cap), torch.int32),
-                               ((G, cap), torch.int32), ((G, cap), torch.int32))
+        prep.r_p = torch.gather(p_idx, 1, prep.row_first.long().clamp_(max=cap - 1)).contiguous()
+        z = zeros_many(dev, ((G, row_cap), torch.float32), ((G, row_cap), torch.int32), ((G, row_cap), torch.int32),
+                       ((G, cap), torch.int32), ((G, cap), torch.int32))
+        prep.sum_row, prep.nv_row, prep.rk_row, prep.n_valid, prep.rank = z if want_logs else (z[0], None, None, None, None)
         # the normalised target is a property of the TARGET ROW (shared by every token and group that points at it)
-        pn_rows, p_norm = l2norm_rows(p_rows.contiguous(), torch.bfloat16, want_norms=True)
-        prep["pn"] = (pn_rows, 1.0 / p_norm)
+        prep.pn_rows, p_norm = l2norm_rows(p_rows.contiguous(), torch.bfloat16, want_norms=True)
+        prep.p_inv = 1.0 / p_norm
 
     def backward_buffers():         # zero / +inf fills that wait for nothing: (dq, dp, d_negs, d_scale, lw_row)
         dq, dp, dn, dls = zeros_many(dev, ((int(n_q_rows), D), torch.float32), ((p_rows.shape[0], D), torch.float32),
                                      ((G, n_neg, D), torch.float32), ((1,), torch.float32))
-        prep["bwd"] = (dq, dp, dn, dls, torch.full((G, row_cap), float("inf"), dtype=torch.float32, device=dev))
+        prep.bwd = (dq, dp, dn, dls, torch.full((G, row_cap), float("inf"), dtype=torch.float32, device=dev))
 
     return prep, [row_maps, fix_bits, rows_and_zeros] + ([backward_buffers] if n_q_rows is not None else [])
 
@@ -921,42 +964,28 @@ def nce_shared_prepare(q_idx, p_idx, n_tok_dev, p_rows, negs, thres, p_row_mask,
     return prep
 
 
-def _nce_fwd_shared(sv, q_rows, p_rows, negs, logit_scale, thres, want_logs, bucket_idx, n_buckets, log_group, p_row_mask, loss,
-                    window=None, prep=None):
-    """Query-row sharing (csrc/nce_shared.hip): the streaming kernels see each distinct query row once."""
-    dev = negs.device
-    G, n_neg, D = sv.groups, sv.n_neg, sv.dim              # negs itself is padded to whole 32-row tiles
-    cap, tok_cap, n_tok_dev = sv.cap, sv.tok_cap, sv.n_tok_dev
-    q_idx, p_idx = sv.q_idx, sv.p_idx
-    row_cap = cap + 32
-    n_p_rows = p_rows.shape[0]
-    rp_pad = (n_p_rows + 255) // 256 * 256
-    n_tiles = (n_neg + 31) // 32
-    st = _stream()
-    key = (q_idx.data_ptr(), p_idx.data_ptr(), p_rows.data_ptr(), negs.data_ptr(), float(thres), bool(want_logs))
-    if prep is not None and prep["key"] != key:
+def _nce_fwd_shared(c, q_rows, p_rows, logit_scale, want_logs, log_group, p_row_mask, window, prep):
+    """Query-row sharing (csrc/nce_shared.hip): the streaming kernels see each distinct query row once.  c: the record's common fields
+    (n_neg: the pool's own size, negs is padded).  -> (record class, its own fields, the sums for mhr_nce_finalize, n_valid, rank)."""
+    G, cap, D, n_neg, thres, dev = c.groups, c.cap, c.dim, c.n_neg, c.thres, c.negs.device
+    q_idx, p_idx, negs, n_tok_dev, s_pos = c.q_idx, c.p_idx, c.negs, c.n_tok_dev, c.s_pos
+    row_cap, st = cap + 32, _stream()
+    n_p_rows, rp_pad, n_tiles = _fix_table_geometry(p_rows, n_neg)
+    if prep is not None and prep.key != _prep_key(q_idx, p_idx, p_rows, negs, thres, want_logs):
         raise ValueError("nce_fwd: prep was built for other token lists / target rows / negatives than this call's")
     if prep is None:
         prep, stages = _shared_prepare_stages(q_idx, p_idx, n_tok_dev, p_rows, negs, n_neg, thres, p_row_mask, want_logs)
         for f in stages:
             f()
-    r_q, tok2row, r_first, n_row = prep["row_maps"]
-    # (1) the real false-negative bit table, per target row
-    fix_words, fix_any, slot_of_row = prep["fix"]
+    # (1) prep.fix_words: the real false-negative bit table, per target row
     # (2) the fused streaming forward over the ROWS with NOTHING suppressed (mhr_nce_fwd's plain form: no bit table, no
     #     suppression words, no normalised-target rows written); its positive is the target of the row's first token, so the
     #     log counters of offset-0 tokens come out of this launch.  Pools that are not whole 32-negative tiles take the
     #     general form with an all-zero bit table that is never written.
-    plain = n_neg % 32 == 0
-    r_p, z = prep["r_p"], prep["z"]
-    sum_row = z[0]
-    nv_row, rk_row = (z[1], z[2]) if want_logs else (None, None)
     qn_row = torch.empty(G, row_cap, D, dtype=torch.bfloat16, device=dev)
-    q_inv_row = torch.empty(G, row_cap, dtype=torch.float32, device=dev)
-    p_inv_row = torch.empty(G, row_cap, dtype=torch.float32, device=dev)
-    s_pos_row = torch.empty(G, row_cap, dtype=torch.float32, device=dev)
+    q_inv_row, p_inv_row, s_pos_row = (torch.empty(G, row_cap, dtype=torch.float32, device=dev) for _ in range(3))
     u_row = torch.empty(G, row_cap, D, dtype=torch.float32, device=dev)
-    if plain:
+    if n_neg % 32 == 0:
         pn_row = supp_row = None
         fix_args = (0, 0, 0, 0)
     else:
@@ -968,34 +997,43 @@ def _nce_fwd_shared(sv, q_rows, p_rows, negs, logit_scale, thres, want_logs, buc
         fix_args = tuple(t.data_ptr() for t in _ZERO_FIX[zkey])
         pn_row = torch.empty(G, row_cap, D, dtype=torch.bfloat16, device=dev)
         supp_row = torch.empty(G, n_tiles, row_cap, dtype=torch.int32, device=dev)
-    _timed_call("mhr_nce_fwd", q_rows.data_ptr(), r_q.data_ptr(), p_rows.data_ptr(), r_p.data_ptr(), _dt(q_rows),
-                negs.data_ptr(), n_neg, D, G, n_row.data_ptr(), row_cap, logit_scale.data_ptr(), float(thres),
-                sum_row.data_ptr(), _ptr(nv_row), _ptr(rk_row), qn_row.data_ptr(), _ptr(pn_row), _ptr(supp_row),
+    _timed_call("mhr_nce_fwd", q_rows.data_ptr(), prep.row_q.data_ptr(), p_rows.data_ptr(), prep.r_p.data_ptr(), _dt(q_rows),
+                negs.data_ptr(), n_neg, D, G, prep.n_row.data_ptr(), row_cap, logit_scale.data_ptr(), float(thres),
+                prep.sum_row.data_ptr(), _ptr(prep.nv_row), _ptr(prep.rk_row), qn_row.data_ptr(), _ptr(pn_row), _ptr(supp_row),
                 q_inv_row.data_ptr(), p_inv_row.data_ptr(), s_pos_row.data_ptr(), int(log_group), u_row.data_ptr(), n_p_rows,
                 *fix_args, st)
-    # (3) per token: s+, sums and counters with the token's own suppressed negatives taken out.  The normalised target is a
-    #     property of the TARGET ROW (shared by every token and group that points at it): one l2norm pass over p_rows
-    pn_rows, sv.p_inv = prep["pn"]
-    sv.pn = pn_rows
+    # (3) per token: s+, sums and counters with the token's own suppressed negatives taken out, against prep.pn_rows (one
+    #     l2norm pass over p_rows: the normalised target is a property of the TARGET ROW)
     ssum = torch.empty(G, cap, dtype=torch.float32, device=dev)
-    n_valid, rank = (z[3], z[4]) if want_logs else (None, None)
-    _timed_call("mhr_nce_shared_fwd_tokens", pn_rows.data_ptr(), n_p_rows, p_idx.data_ptr(), tok2row.data_ptr(), G,
-                n_tok_dev.data_ptr(), cap, row_cap, qn_row.data_ptr(), sum_row.data_ptr(), _ptr(nv_row), _ptr(rk_row),
-                negs.data_ptr(), n_neg, D, logit_scale.data_ptr(), fix_words.data_ptr(), _ptr(slot_of_row), fix_any.data_ptr(),
-                sv.s_pos.data_ptr(), ssum.data_ptr(), _ptr(n_valid), _ptr(rank), st)
-    lib.call("mhr_nce_finalize", ssum.data_ptr(), sv.s_pos.data_ptr(), G, n_tok_dev.data_ptr(), cap,
-             logit_scale.data_ptr(), loss.data_ptr(), sv.lse.data_ptr(), _ptr(n_valid), _ptr(bucket_idx), int(n_buckets),
-             _ptr(sv.bucket_sum), _ptr(sv.bucket_cnt), st)
-    sv.shared = True
-    sv.bwd_bufs = prep.get("bwd")
-    sv.qn, sv.u, sv.q_inv, sv.supp = qn_row, u_row, q_inv_row, supp_row
-    sv.tok2row, sv.row_first, sv.n_row_dev, sv.row_cap, sv.row_q = tok2row, r_first, n_row, row_cap, r_q
-    sv.window = window                      # (tok_of_slot [G, n_slots], L, P) of window-structured lists, or None
-    sv.fix_words, sv.fix_slot, sv.fix_any, sv.n_p_rows = fix_words, slot_of_row, fix_any, n_p_rows
-    sv.loss = loss[:, :tok_cap]
-    sv.n_valid = None if n_valid is None else n_valid[:, :tok_cap]
-    sv.rank = None if rank is None else rank[:, :tok_cap]
-    return sv
+    _timed_call("mhr_nce_shared_fwd_tokens", prep.pn_rows.data_ptr(), n_p_rows, p_idx.data_ptr(), prep.tok2row.data_ptr(), G,
+                n_tok_dev.data_ptr(), cap, row_cap, qn_row.data_ptr(), prep.sum_row.data_ptr(), _ptr(prep.nv_row), _ptr(prep.rk_row),
+                negs.data_ptr(), n_neg, D, logit_scale.data_ptr(), prep.fix_words.data_ptr(), _ptr(prep.slot_of_row),
+                prep.fix_any.data_ptr(), s_pos.data_ptr(), ssum.data_ptr(), _ptr(prep.n_valid), _ptr(prep.rank), st)
+    own = dict(qn=qn_row, u=u_row, q_inv=q_inv_row, supp=supp_row, pn=prep.pn_rows, p_inv=prep.p_inv, tok2row=prep.tok2row,
+               row_first=prep.row_first, row_q=prep.row_q, n_row_dev=prep.n_row, row_cap=row_cap, fix_words=prep.fix_words,
+               fix_slot=prep.slot_of_row, fix_any=prep.fix_any, n_p_rows=n_p_rows, window=window, bwd_bufs=prep.bwd)
+    return NceSavedShared, own, ssum, prep.n_valid, prep.rank
+
+
+def _nce_fwd_tokens(c, q_rows, p_rows, logit_scale, log_group, p_row_mask, n_valid, rank):
+    """The per-token streaming kernels (csrc/nce.hip); arguments and result as for _nce_fwd_shared."""
+    G, cap, D, n_neg, dev = c.groups, c.cap, c.dim, c.n_neg, c.negs.device
+    n_p_rows, rp_pad, n_tiles = _fix_table_geometry(p_rows, n_neg)
+    qn, pn = (torch.empty(G, cap, D, dtype=torch.bfloat16, device=dev) for _ in range(2))
+    q_inv, p_inv = (torch.empty(G, cap, dtype=torch.float32, device=dev) for _ in range(2))
+    supp = torch.empty(G, n_tiles, cap, dtype=torch.int32, device=dev)
+    u = torch.empty(G, cap, D, dtype=torch.float32, device=dev)  # unnormalised token-side gradient (fused forward)
+    ssum = torch.zeros(G, cap, dtype=torch.float32, device=dev)
+    # hoisted form (mhr.h): the false-negative test runs once per (group, target row, negative) into a bit table.  The table is
+    # the exhaustive one, built inside mhr_nce_fwd: the token kernel reads every word of it
+    fix_words = torch.empty(G, n_tiles, rp_pad, dtype=torch.int32, device=dev)
+    row_list, n_list, slot_of_row = _p_row_lists(p_row_mask, G, n_p_rows, rp_pad)
+    _timed_call("mhr_nce_fwd", q_rows.data_ptr(), c.q_idx.data_ptr(), p_rows.data_ptr(), c.p_idx.data_ptr(), _dt(q_rows),
+                c.negs.data_ptr(), n_neg, D, G, c.n_tok_dev.data_ptr(), cap, logit_scale.data_ptr(), c.thres,
+                ssum.data_ptr(), _ptr(n_valid), _ptr(rank), qn.data_ptr(), pn.data_ptr(),
+                supp.data_ptr(), q_inv.data_ptr(), p_inv.data_ptr(), c.s_pos.data_ptr(), int(log_group), u.data_ptr(),
+                n_p_rows, fix_words.data_ptr(), _ptr(row_list), _ptr(n_list), _ptr(slot_of_row), _stream())
+    return NceSavedTokens, dict(qn=qn, pn=pn, q_inv=q_inv, p_inv=p_inv, u=u, supp=supp), ssum, n_valid, rank
 
 
 def nce_fwd(q_rows, q_idx, p_rows, p_idx, negs, n_tok_dev, tok_cap, logit_scale, thres=0.99, want_logs=False,
@@ -1016,10 +1054,9 @@ def nce_fwd(q_rows, q_idx, p_rows, p_idx, negs, n_tok_dev, tok_cap, logit_scale,
     if q_idx.dim() == 1:
         q_idx, p_idx, negs, n_tok_dev = q_idx[None], p_idx[None], negs[None], n_tok_dev.view(1)
     _chk(negs, "negs", torch.bfloat16)
-    _chk(q_idx, "q_idx", torch.int32)
-    _chk(p_idx, "p_idx", torch.int32)
-    _chk(n_tok_dev, "n_tok_dev", torch.int32)
     _chk(logit_scale, "logit_scale", torch.float32)
+    for t, name in ((q_idx, "q_idx"), (p_idx, "p_idx"), (n_tok_dev, "n_tok_dev")):
+        _chk(t, name, torch.int32)
     assert q_rows.dtype == p_rows.dtype
     dev = negs.device
     G, n_neg, D = negs.shape
@@ -1033,74 +1070,31 @@ def nce_fwd(q_rows, q_idx, p_rows, p_idx, negs, n_tok_dev, tok_cap, logit_scale,
         p_idx = torch.nn.functional.pad(p_idx, (0, cap - tok_cap)).contiguous()
         if bucket_idx is not None:
             bucket_idx = torch.nn.functional.pad(bucket_idx, (0, cap - tok_cap)).contiguous()
-    sv = NceSaved()
-    sv.shared = False
-    sv.bwd_bufs = None
-    sv.q_idx, sv.p_idx = q_idx, p_idx
-    sv.ihn_beta = float(ihn_beta)
-    sv.wide = D not in STREAM_DIMS or sv.ihn_beta > 0     # feature dims beyond the register-stationary kernels (and the IHN loss): wide.py
-    sv.bucket_idx, sv.n_buckets, sv.bucket_sum, sv.bucket_cnt = bucket_idx, int(n_buckets), None, None
-    shared_path = share_rows and SHARE_ROWS and D in STREAM_DIMS and float(ihn_beta) <= 0
-    zf = zeros_many(dev, ((2, G, max(n_buckets, 1)), torch.float32), ((G, cap), torch.float32), ((G, cap), torch.float32),
-                    ((G, cap) if (want_logs and not shared_path) else (1,), torch.int32),
-                    ((G, cap) if (want_logs and not shared_path) else (1,), torch.int32))
-    if bucket_idx is not None:       # per-(group, bucket) loss sums and token counts come out of the finalize kernel
+    if bucket_idx is not None:
         _chk(bucket_idx, "bucket_idx", torch.int32)
         assert bucket_idx.shape == (G, cap)
-        sv.bucket_sum, sv.bucket_cnt = zf[0][0], zf[0][1]
-    loss = zf[1]
-    sv.lse = zf[2]
-    n_valid = zf[3] if want_logs else None           # (the row-sharing path brings its own per-token counters)
-    rank = zf[4] if want_logs else None
-    sv.s_pos = torch.empty(G, cap, dtype=torch.float32, device=dev)
-    if sv.ihn_beta > 0:
-        sv.ihn_num = torch.zeros(G, cap, dtype=torch.float32, device=dev)
-        sv.ihn_imp = torch.zeros(G, cap, dtype=torch.float32, device=dev)
-    if share_rows and SHARE_ROWS and not sv.wide:
-        sv.negs = negs
-        sv.n_tok_dev, sv.tok_cap, sv.cap, sv.thres, sv.dim, sv.n_neg, sv.groups = n_tok_dev, tok_cap, cap, float(thres), D, n_neg, G
-        return _nce_fwd_shared(sv, q_rows, p_rows, negs, logit_scale, thres, want_logs, bucket_idx, n_buckets, log_group,
-                               p_row_mask, loss, window, prep)
-    sv.qn = torch.empty(G, cap, D, dtype=torch.bfloat16, device=dev)
-    sv.pn = torch.empty(G, cap, D, dtype=torch.bfloat16, device=dev)
-    sv.q_inv = torch.empty(G, cap, dtype=torch.float32, device=dev)
-    sv.p_inv = torch.empty(G, cap, dtype=torch.float32, device=dev)
-    sv.supp = sv.u = None
-    if not sv.wide:
-        sv.supp = torch.empty(G, (n_neg + 31) // 32, cap, dtype=torch.int32, device=dev)
-        sv.u = torch.empty(G, cap, D, dtype=torch.float32, device=dev)  # unnormalised token-side gradient (fused forward)
-    sv.negs = negs
-    sv.n_tok_dev, sv.tok_cap, sv.cap, sv.thres, sv.dim, sv.n_neg, sv.groups = n_tok_dev, tok_cap, cap, float(thres), D, n_neg, G
-    if sv.wide:
+    path = nce_path(D, share_rows, ihn_beta)
+    own_logs = want_logs and path != "shared"         # (the row-sharing path brings its own per-token counters)
+    zf = zeros_many(dev, ((2, G, max(n_buckets, 1)), torch.float32), ((G, cap), torch.float32), ((G, cap), torch.float32),
+                    ((G, cap) if own_logs else (1,), torch.int32), ((G, cap) if own_logs else (1,), torch.int32))
+    bucket_sum, bucket_cnt = (zf[0][0], zf[0][1]) if bucket_idx is not None else (None, None)    # (written by the finalize kernel)
+    loss, lse = zf[1], zf[2]
+    n_valid, rank = (zf[3], zf[4]) if own_logs else (None, None)
+    s_pos = torch.empty(G, cap, dtype=torch.float32, device=dev)
+    c = types.SimpleNamespace(q_idx=q_idx, p_idx=p_idx, n_tok_dev=n_tok_dev, tok_cap=tok_cap, cap=cap, groups=G, dim=D, n_neg=n_neg,
+                              thres=float(thres), negs=negs, lse=lse, s_pos=s_pos, bucket_idx=bucket_idx, n_buckets=int(n_buckets),
+                              bucket_sum=bucket_sum, bucket_cnt=bucket_cnt)
+    if path == "wide":
         from . import wide
-        wide.nce_fwd_wide(sv, q_rows, p_rows, negs, logit_scale, want_logs, bucket_idx, loss, n_valid, rank)
-        sv.loss = loss[:, :tok_cap]
-        sv.n_valid = None if n_valid is None else n_valid[:, :tok_cap]
-        sv.rank = None if rank is None else rank[:, :tok_cap]
-        return sv
-    ssum = torch.zeros(G, cap, dtype=torch.float32, device=dev)
-    st = _stream()
-    # hoisted form (mhr.h): the false-negative test runs once per (group, target row, negative) into a bit table.  The table is
-    # the exhaustive one, built inside mhr_nce_fwd: the token kernel reads every word of it
-    n_p_rows = p_rows.shape[0]
-    rp_pad = (n_p_rows + 255) // 256 * 256
-    fix_words = torch.empty(G, (n_neg + 31) // 32, rp_pad, dtype=torch.int32, device=dev)
-    row_list = n_list = slot_of_row = None
-    if p_row_mask is not None:
-        row_list, n_list = _p_row_lists(p_row_mask, G, n_p_rows, rp_pad)
-        slot_of_row = torch.zeros(G, n_p_rows, dtype=torch.int32, device=dev)     # zero: any lookup stays in bounds
-    _timed_call("mhr_nce_fwd", q_rows.data_ptr(), q_idx.data_ptr(), p_rows.data_ptr(), p_idx.data_ptr(), _dt(q_rows),
-                negs.data_ptr(), n_neg, D, G, n_tok_dev.data_ptr(), cap, logit_scale.data_ptr(), float(thres),
-                ssum.data_ptr(), _ptr(n_valid), _ptr(rank), sv.qn.data_ptr(), sv.pn.data_ptr(),
-                sv.supp.data_ptr(), sv.q_inv.data_ptr(), sv.p_inv.data_ptr(), sv.s_pos.data_ptr(), int(log_group), sv.u.data_ptr(),
-                n_p_rows, fix_words.data_ptr(), _ptr(row_list), _ptr(n_list), _ptr(slot_of_row), st)
-    lib.call("mhr_nce_finalize", ssum.data_ptr(), sv.s_pos.data_ptr(), G, n_tok_dev.data_ptr(), cap,
-             logit_scale.data_ptr(), loss.data_ptr(), sv.lse.data_ptr(), _ptr(n_valid), _ptr(bucket_idx), int(n_buckets),
-             _ptr(sv.bucket_sum), _ptr(sv.bucket_cnt), st)
-    sv.loss = loss[:, :tok_cap]
-    sv.n_valid = None if n_valid is None else n_valid[:, :tok_cap]
-    sv.rank = None if rank is None else rank[:, :tok_cap]
-    return sv
+        return wide.nce_fwd_wide(c, q_rows, p_rows, logit_scale, want_logs, float(ihn_beta), loss, n_valid, rank)
+    if path == "shared":
+        cls, own, ssum, n_valid, rank = _nce_fwd_shared(c, q_rows, p_rows, logit_scale, want_logs, log_group, p_row_mask, window, prep)
+    else:
+        cls, own, ssum, n_valid, rank = _nce_fwd_tokens(c, q_rows, p_rows, logit_scale, log_group, p_row_mask, n_valid, rank)
+    lib.call("mhr_nce_finalize", ssum.data_ptr(), s_pos.data_ptr(), G, n_tok_dev.data_ptr(), cap,
+             logit_scale.data_ptr(), loss.data_ptr(), lse.data_ptr(), _ptr(n_valid), _ptr(bucket_idx), int(n_buckets),
+             _ptr(bucket_sum), _ptr(bucket_cnt), _stream())
+    return cls(loss, n_valid, rank, **vars(c), **own)
 
 
 def nce_bwd(sv, w, logit_scale, q_idx, p_idx, dq_rows, dp_rows, d_negs=None, d_logit_scale=None, want_negs=True, lw_row=None,
@@ -1127,54 +1121,65 @@ def nce_bwd(sv, w, logit_scale, q_idx, p_idx, dq_rows, dp_rows, d_negs=None, d_l
     _chk(w, "w", torch.float32)
     _chk(dq_rows, "dq_rows", torch.float32)
     _chk(dp_rows, "dp_rows", torch.float32)
+    wb_ptr, nb = (sv.bucket_idx.data_ptr(), sv.n_buckets) if bucketed else (0, 0)      # per-bucket weights: the kernels look them up
     if sv.wide:
         from . import wide
         w_tok = torch.gather(w, 1, sv.bucket_idx.long().clamp(0, sv.n_buckets - 1)) if bucketed else w
         wide.nce_bwd_wide(sv, w_tok, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale)
-        return d_negs, d_logit_scale
-    st = _stream()
-    if sv.shared:
-        wb_ptr, nb = (sv.bucket_idx.data_ptr(), sv.n_buckets) if bucketed else (0, 0)
-        dn_ptr = d_negs.data_ptr() if want_negs else 0
-        if lw_row is None:                   # (+inf: a row the kernels do not visit contributes nothing to the negative-side product)
-            lw_row = torch.full((G, sv.row_cap), float("inf"), dtype=torch.float32, device=dev)
-        assert lw_row.shape == (G, sv.row_cap)
-        dn_fix = dls_part = None
-        if DETERMINISTIC and sv.window is not None:
-            dn_fix = torch.zeros(d_negs.shape, dtype=torch.int64, device=dev) if want_negs else None
-            dls_part = torch.zeros(G * 1024, dtype=torch.float32, device=dev)
-        if sv.window is not None:            # window-structured lists: sums formed where they land, no per-token atomics
-            tos, L_, P_ = sv.window
-            _timed_call("mhr_nce_shared_bwd_rows", sv.qn.data_ptr(), sv.u.data_ptr(), sv.q_inv.data_ptr(), sv.row_q.data_ptr(),
-                        sv.row_first.data_ptr(), sv.n_row_dev.data_ptr(), sv.row_cap, sv.pn.data_ptr(), D, G, cap,
-                        logit_scale.data_ptr(), sv.lse.data_ptr(), w.data_ptr(), sv.s_pos.data_ptr(), sv.p_idx.data_ptr(),
-                        dq_rows.data_ptr(), d_logit_scale.data_ptr(), lw_row.data_ptr(), wb_ptr, nb, sv.negs.data_ptr(), sv.n_neg,
-                        sv.fix_words.data_ptr(), sv.n_p_rows, _ptr(sv.fix_slot), sv.fix_any.data_ptr(), dn_ptr,
-                        1 if exclusive_q_rows else 0, _ptr(dn_fix), _ptr(dls_part), st)
-            if dls_part is not None:         # the workgroups' partials of d(logit_scale), folded in index order
-                lib.call("mhr_det_sum_into", dls_part.data_ptr(), dls_part.numel(), logit_scale.data_ptr(), 1, d_logit_scale.data_ptr(), st)
-            _timed_call("mhr_nce_shared_bwd_targets", sv.qn.data_ptr(), sv.row_cap, sv.tok2row.data_ptr(), tos.data_ptr(),
-                        sv.n_tok_dev.data_ptr(), G, tos.shape[1], cap, int(L_), int(P_), sv.pn.data_ptr(), sv.p_inv.data_ptr(), D,
-                        logit_scale.data_ptr(), sv.lse.data_ptr(), w.data_ptr(), sv.s_pos.data_ptr(), wb_ptr, nb, sv.n_p_rows,
-                        dp_rows.data_ptr(), st)
-        else:
-            lw_tok = torch.empty(G, cap, dtype=torch.float32, device=dev)
-            _timed_call("mhr_nce_shared_bwd_tokens", sv.qn.data_ptr(), sv.u.data_ptr(), sv.q_inv.data_ptr(), sv.row_cap,
-                        sv.tok2row.data_ptr(), sv.pn.data_ptr(), D, G, sv.n_tok_dev.data_ptr(), cap, logit_scale.data_ptr(),
-                        sv.lse.data_ptr(), w.data_ptr(), sv.p_inv.data_ptr(), sv.s_pos.data_ptr(), sv.q_idx.data_ptr(),
-                        sv.p_idx.data_ptr(), dq_rows.data_ptr(), dp_rows.data_ptr(), d_logit_scale.data_ptr(), lw_tok.data_ptr(),
-                        wb_ptr, nb, sv.negs.data_ptr(), sv.n_neg, sv.fix_words.data_ptr(), sv.n_p_rows, _ptr(sv.fix_slot),
-                        sv.fix_any.data_ptr(), dn_ptr, st)
-            if want_negs:
-                lib.call("mhr_nce_row_lw", lw_tok.data_ptr(), sv.row_first.data_ptr(), sv.n_row_dev.data_ptr(), G, cap, sv.row_cap,
-                         lw_row.data_ptr(), st)
+    elif sv.shared:
+        _nce_bwd_shared(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale, want_negs, lw_row, exclusive_q_rows)
+    else:
+        _nce_bwd_tokens(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale, want_negs)
+    return d_negs, d_logit_scale
+
+
+def _nce_bwd_shared(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale, want_negs, lw_row, exclusive_q_rows):
+    """Row-wise / target-wise kernels for window-structured lists, else per-token atomics; then the negative-side product over the rows."""
+    dev, D, cap, G, st = sv.negs.device, sv.dim, sv.cap, sv.groups, _stream()
+    dn_ptr = d_negs.data_ptr() if want_negs else 0
+    if lw_row is None:                   # (+inf: a row the kernels do not visit contributes nothing to the negative-side product)
+        lw_row = torch.full((G, sv.row_cap), float("inf"), dtype=torch.float32, device=dev)
+    assert lw_row.shape == (G, sv.row_cap)
+    dn_fix = dls_part = None
+    if DETERMINISTIC and sv.window is not None:
+        dn_fix = torch.zeros(d_negs.shape, dtype=torch.int64, device=dev) if want_negs else None
+        dls_part = torch.zeros(G * 1024, dtype=torch.float32, device=dev)
+    if sv.window is not None:            # window-structured lists: sums formed where they land, no per-token atomics
+        tos, L_, P_ = sv.window
+        _timed_call("mhr_nce_shared_bwd_rows", sv.qn.data_ptr(), sv.u.data_ptr(), sv.q_inv.data_ptr(), sv.row_q.data_ptr(),
+                    sv.row_first.data_ptr(), sv.n_row_dev.data_ptr(), sv.row_cap, sv.pn.data_ptr(), D, G, cap,
+                    logit_scale.data_ptr(), sv.lse.data_ptr(), w.data_ptr(), sv.s_pos.data_ptr(), sv.p_idx.data_ptr(),
+                    dq_rows.data_ptr(), d_logit_scale.data_ptr(), lw_row.data_ptr(), wb_ptr, nb, sv.negs.data_ptr(), sv.n_neg,
+                    sv.fix_words.data_ptr(), sv.n_p_rows, _ptr(sv.fix_slot), sv.fix_any.data_ptr(), dn_ptr,
+                    1 if exclusive_q_rows else 0, _ptr(dn_fix), _ptr(dls_part), st)
+        if dls_part is not None:         # the workgroups' partials of d(logit_scale), folded in index order
+            lib.call("mhr_det_sum_into", dls_part.data_ptr(), dls_part.numel(), logit_scale.data_ptr(), 1, d_logit_scale.data_ptr(), st)
+        _timed_call("mhr_nce_shared_bwd_targets", sv.qn.data_ptr(), sv.row_cap, sv.tok2row.data_ptr(), tos.data_ptr(),
+                    sv.n_tok_dev.data_ptr(), G, tos.shape[1], cap, int(L_), int(P_), sv.pn.data_ptr(), sv.p_inv.data_ptr(), D,
+                    logit_scale.data_ptr(), sv.lse.data_ptr(), w.data_ptr(), sv.s_pos.data_ptr(), wb_ptr, nb, sv.n_p_rows,
+                    dp_rows.data_ptr(), st)
+    else:
+        lw_tok = torch.empty(G, cap, dtype=torch.float32, device=dev)
+        _timed_call("mhr_nce_shared_bwd_tokens", sv.qn.data_ptr(), sv.u.data_ptr(), sv.q_inv.data_ptr(), sv.row_cap,
+                    sv.tok2row.data_ptr(), sv.pn.data_ptr(), D, G, sv.n_tok_dev.data_ptr(), cap, logit_scale.data_ptr(),
+                    sv.lse.data_ptr(), w.data_ptr(), sv.p_inv.data_ptr(), sv.s_pos.data_ptr(), sv.q_idx.data_ptr(),
+                    sv.p_idx.data_ptr(), dq_rows.data_ptr(), dp_rows.data_ptr(), d_logit_scale.data_ptr(), lw_tok.data_ptr(),
+                    wb_ptr, nb, sv.negs.data_ptr(), sv.n_neg, sv.fix_words.data_ptr(), sv.n_p_rows, _ptr(sv.fix_slot),
+                    sv.fix_any.data_ptr(), dn_ptr, st)
         if want_negs:
-            _timed_call("mhr_nce_bwd_negs", sv.qn.data_ptr(), sv.negs.data_ptr(), _ptr(sv.supp), sv.n_neg, D, G,
-                        sv.n_row_dev.data_ptr(), sv.row_cap, logit_scale.data_ptr(), lw_row.data_ptr(), d_negs.data_ptr(),
-                        _ptr(dn_fix), st)
-            if dn_fix is not None:           # fixed-point accumulators (tiles + suppressed-pair corrections) -> d_negs
-                lib.call("mhr_det_flush", dn_fix.data_ptr(), d_negs.data_ptr(), d_negs.numel(), st)
-        return d_negs, d_logit_scale
+            lib.call("mhr_nce_row_lw", lw_tok.data_ptr(), sv.row_first.data_ptr(), sv.n_row_dev.data_ptr(), G, cap, sv.row_cap,
+                     lw_row.data_ptr(), st)
+    if want_negs:
+        _timed_call("mhr_nce_bwd_negs", sv.qn.data_ptr(), sv.negs.data_ptr(), _ptr(sv.supp), sv.n_neg, D, G,
+                    sv.n_row_dev.data_ptr(), sv.row_cap, logit_scale.data_ptr(), lw_row.data_ptr(), d_negs.data_ptr(),
+                    _ptr(dn_fix), st)
+        if dn_fix is not None:           # fixed-point accumulators (tiles + suppressed-pair corrections) -> d_negs
+            lib.call("mhr_det_flush", dn_fix.data_ptr(), d_negs.data_ptr(), d_negs.numel(), st)
+
+
+def _nce_bwd_tokens(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale, want_negs):
+    """Per-token backward: the token kernel (dq, dp, d(logit_scale), the row weights), then the negative-side product."""
+    dev, D, cap, G, st = sv.negs.device, sv.dim, sv.cap, sv.groups, _stream()
     lw = torch.empty(G, cap, dtype=torch.float32, device=dev)     # lse log2e - log2 w: written by bwd_tokens, read by bwd_negs
     dq_fix = dp_fix = dls_part = dn_fix = None
     if DETERMINISTIC:             # order-independent accumulation (include/mhr.h: deterministic mode)
@@ -1185,8 +1190,8 @@ def nce_bwd(sv, w, logit_scale, q_idx, p_idx, dq_rows, dp_rows, d_negs=None, d_l
     _timed_call("mhr_nce_bwd_tokens", sv.qn.data_ptr(), sv.pn.data_ptr(), sv.u.data_ptr(), D,
                 G, sv.n_tok_dev.data_ptr(), cap, logit_scale.data_ptr(), sv.lse.data_ptr(), w.data_ptr(), sv.q_inv.data_ptr(),
                 sv.p_inv.data_ptr(), sv.s_pos.data_ptr(), sv.q_idx.data_ptr(), sv.p_idx.data_ptr(), dq_rows.data_ptr(),
-                dp_rows.data_ptr(), d_logit_scale.data_ptr(), lw.data_ptr(), sv.bucket_idx.data_ptr() if bucketed else 0,
-                sv.n_buckets if bucketed else 0, _ptr(dq_fix), _ptr(dp_fix), _ptr(dls_part), st)
+                dp_rows.data_ptr(), d_logit_scale.data_ptr(), lw.data_ptr(), wb_ptr, nb, _ptr(dq_fix), _ptr(dp_fix),
+                _ptr(dls_part), st)
     if dq_fix is not None:
         lib.call("mhr_det_flush", dq_fix.data_ptr(), dq_rows.data_ptr(), dq_rows.numel(), st)
         lib.call("mhr_det_flush", dp_fix.data_ptr(), dp_rows.data_ptr(), dp_rows.numel(), st)
@@ -1196,7 +1201,6 @@ def nce_bwd(sv, w, logit_scale, q_idx, p_idx, dq_rows, dp_rows, d_negs=None, d_l
                     sv.n_tok_dev.data_ptr(), cap, logit_scale.data_ptr(), lw.data_ptr(), d_negs.data_ptr(), _ptr(dn_fix), st)
         if dn_fix is not None:
             lib.call("mhr_det_flush", dn_fix.data_ptr(), d_negs.data_ptr(), d_negs.numel(), st)
-    return d_negs, d_logit_scale
 
 
 # ------------------------------------------------------------------------------------------------

@@ -46,10 +46,10 @@ def _norm_rows(rows, idx):
     return (x * inv[:, None]).to(torch.bfloat16), inv
 
 
-def _live_cap(sv):
+def _live_cap(n_tok_dev, cap):
     """Rows worth visiting: the largest live count over the groups, rounded up to 256 (one host sync)."""
-    n_max = int(sv.n_tok_dev.max())
-    return min(sv.cap, -(-max(n_max, 1) // 256) * 256)
+    n_max = int(n_tok_dev.max())
+    return min(cap, -(-max(n_max, 1) // 256) * 256)
 
 
 MFMA_NCE = os.environ.get("MHR_NCE_WIDE_MFMA", "1") != "0"     # 0: the library-GEMM + fp32-chunk form of the logit products
@@ -60,10 +60,10 @@ MFMA_NCE = os.environ.get("MHR_NCE_WIDE_MFMA", "1") != "0"     # 0: the library-
 OWN_GEMM = os.environ.get("MHR_NCE_WIDE_GEMM", "lib") == "own"
 
 
-def _mfma_path(sv, D):
+def _mfma_path(D, ihn_beta):
     """The hand-written contraction (csrc/nce_wide.hip) serves every feature dim that is a multiple of 64; REMI's
     hard-negative loss keeps the dense chunk path (its two-pass logsumexp epilogue)."""
-    return MFMA_NCE and D % 64 == 0 and D <= 8192 and sv.ihn_beta <= 0
+    return MFMA_NCE and D % 64 == 0 and D <= 8192 and ihn_beta <= 0
 
 
 def _pad_rows(x, t_pad):
@@ -75,30 +75,30 @@ def _pad_rows(x, t_pad):
     return out
 
 
-def nce_fwd_wide(sv, q_rows, p_rows, negs, logit_scale, want_logs, bucket_idx, loss, n_valid, rank):
-    """Fills sv (qn, pn, q_inv, p_inv, s_pos, lse, bucket sums) and loss / n_valid / rank [G, cap] in place."""
+def nce_fwd_wide(sv, q_rows, p_rows, logit_scale, want_logs, ihn_beta, loss, n_valid, rank):
+    """sv: the common fields of the record as ops.nce_fwd prepared them (lse, s_pos and the bucket sums are filled here);
+    loss / n_valid / rank [G, cap]: filled in place.  Returns the ops.NceSavedWide record."""
     from . import ops
-    G, cap, thres = sv.groups, sv.cap, sv.thres
+    G, cap, thres, negs, D, dev = sv.groups, sv.cap, sv.thres, sv.negs, sv.dim, sv.negs.device
+    ihn_num, ihn_imp = (torch.zeros(G, cap, dtype=torch.float32, device=dev) for _ in range(2)) if ihn_beta > 0 else (None, None)
+    qn_all, pn_all = (torch.empty(G, cap, D, dtype=torch.bfloat16, device=dev) for _ in range(2))
+    q_inv, p_inv = (torch.empty(G, cap, dtype=torch.float32, device=dev) for _ in range(2))
     scale = _scale(logit_scale)
-    sv.scale_dev = scale
-    cap_eff = sv.cap_eff = _live_cap(sv)
+    cap_eff = _live_cap(sv.n_tok_dev, cap)
     loss.zero_()
     sv.lse.zero_()
     if want_logs:
         n_valid.zero_()
         rank.zero_()
     st = _stream()
-    D = q_rows.shape[1]
-    mfma = _mfma_path(sv, D)
-    sv.wide_pack = [None] * G if mfma else None
-    dev = negs.device
+    wide_pack = [None] * G if _mfma_path(D, ihn_beta) else None
     for g in range(G):
         qn, qi = _norm_rows(q_rows, sv.q_idx[g, :cap_eff])
         pn, pi = _norm_rows(p_rows, sv.p_idx[g, :cap_eff])
-        sv.qn[g, :cap_eff], sv.pn[g, :cap_eff], sv.q_inv[g, :cap_eff], sv.p_inv[g, :cap_eff] = qn, pn, qi, pi
+        qn_all[g, :cap_eff], pn_all[g, :cap_eff], q_inv[g, :cap_eff], p_inv[g, :cap_eff] = qn, pn, qi, pi
         s_pos = (qn.float() * pn.float()).sum(-1).contiguous()
         sv.s_pos[g, :cap_eff] = s_pos
-        if mfma:
+        if wide_pack is not None:
             # hand-written contraction: targets x negatives -> false-negative bits, queries x negatives -> the per-token sums
             # (one launch each on the packed tile images; no logit block, no library GEMM)
             n_neg = sv.n_neg
@@ -121,17 +121,17 @@ def nce_fwd_wide(sv, q_rows, p_rows, negs, logit_scale, want_logs, bucket_idx, l
             sv.lse[g, :cap_eff], loss[g, :cap_eff] = lse_g[:cap_eff], loss_g[:cap_eff]
             if want_logs:
                 n_valid[g, :cap_eff], rank[g, :cap_eff] = nv_g[:cap_eff], rk_g[:cap_eff]
-            sv.wide_pack[g] = (negs_p, bits, t_pad)
+            wide_pack[g] = (negs_p, bits, t_pad)
             continue
         ngt = negs[g, :sv.n_neg].t()
         for c0 in range(0, cap_eff, CHUNK):
             c1 = min(cap_eff, c0 + CHUNK)
             s = _mm(qn[c0:c1], ngt)                               # cos(query, negative)
             fx = _mm(pn[c0:c1], ngt)                              # cos(target, negative): false-negative test
-            if sv.ihn_beta > 0:                                   # REMI's hard-negative loss: same chunks, its own epilogue
+            if ihn_beta > 0:                                      # REMI's hard-negative loss: same chunks, its own epilogue
                 lib.call("mhr_ihn_dense_fwd", s.data_ptr(), fx.data_ptr(), s.shape[1], sv.n_neg, s_pos[c0:c1].data_ptr(),
-                         scale.data_ptr(), float(thres), float(sv.ihn_beta), sv.n_tok_dev[g:g + 1].data_ptr(), c0, c1 - c0,
-                         sv.lse[g, c0:c1].data_ptr(), sv.ihn_num[g, c0:c1].data_ptr(), sv.ihn_imp[g, c0:c1].data_ptr(),
+                         scale.data_ptr(), float(thres), ihn_beta, sv.n_tok_dev[g:g + 1].data_ptr(), c0, c1 - c0,
+                         sv.lse[g, c0:c1].data_ptr(), ihn_num[g, c0:c1].data_ptr(), ihn_imp[g, c0:c1].data_ptr(),
                          loss[g, c0:c1].data_ptr(), n_valid[g, c0:c1].data_ptr() if want_logs else 0,
                          rank[g, c0:c1].data_ptr() if want_logs else 0, st)
                 continue
@@ -139,29 +139,27 @@ def nce_fwd_wide(sv, q_rows, p_rows, negs, logit_scale, want_logs, bucket_idx, l
                      scale.data_ptr(), float(thres), sv.n_tok_dev[g:g + 1].data_ptr(), c0, c1 - c0, sv.lse[g, c0:c1].data_ptr(),
                      loss[g, c0:c1].data_ptr(), n_valid[g, c0:c1].data_ptr() if want_logs else 0,
                      rank[g, c0:c1].data_ptr() if want_logs else 0, st)
-    if bucket_idx is not None:
+    if sv.bucket_idx is not None:
         live = torch.arange(cap, device=negs.device)[None, :] < sv.n_tok_dev[:, None]
-        flat = (torch.arange(G, device=negs.device)[:, None] * sv.n_buckets + bucket_idx.long().clamp(0, sv.n_buckets - 1)).reshape(-1)
+        flat = (torch.arange(G, device=negs.device)[:, None] * sv.n_buckets + sv.bucket_idx.long().clamp(0, sv.n_buckets - 1)).reshape(-1)
         sv.bucket_sum.view(-1).index_add_(0, flat, loss.reshape(-1))
         sv.bucket_cnt.view(-1).index_add_(0, flat, live.float().reshape(-1))
+    return ops.NceSavedWide(loss, n_valid, rank, **vars(sv), qn=qn_all, pn=pn_all, q_inv=q_inv, p_inv=p_inv, scale_dev=scale,
+                            cap_eff=cap_eff, wide_pack=wide_pack, ihn_beta=ihn_beta, ihn_num=ihn_num, ihn_imp=ihn_imp)
 
 
 def nce_bwd_wide(sv, w_tok, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale):
     """w_tok [G, cap] per-token weights.  Accumulates dq_rows / dp_rows / d_negs / d_logit_scale in place."""
-    G, thres = sv.groups, sv.thres
-    scale = sv.scale_dev
-    cap_eff = sv.cap_eff
-    dev = dq_rows.device
+    G, D, thres, scale, cap_eff, dev = sv.groups, sv.dim, sv.thres, sv.scale_dev, sv.cap_eff, dq_rows.device
     live = torch.arange(cap_eff, device=dev)[None, :] < sv.n_tok_dev[:, None]
     dls = torch.zeros((), dtype=torch.float32, device=dev)
     st = _stream()
     w_tok = w_tok.contiguous()
     from . import ops
-    D = sv.qn.shape[-1]
     for g in range(G):
         ng = sv.negs[g, :sv.n_neg]
         ngt = ng.t()
-        pack = sv.wide_pack[g] if getattr(sv, "wide_pack", None) is not None else None
+        pack = sv.wide_pack[g] if sv.wide_pack is not None else None
         step = cap_eff if pack is not None else CHUNK          # the hand-written tile producer covers all live rows in one launch
         for c0 in range(0, cap_eff, step):
             c1 = min(cap_eff, c0 + step)
@@ -181,18 +179,15 @@ def nce_bwd_wide(sv, w_tok, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale
                 s = _mm(qn, ngt)
                 fx = _mm(pn, ngt)
                 gmat = torch.empty(c1 - c0, sv.n_neg, dtype=torch.bfloat16, device=dev)
-            if pack is not None:
-                pass
-            elif sv.ihn_beta > 0:
-                lib.call("mhr_ihn_dense_bwd", s.data_ptr(), fx.data_ptr(), s.shape[1], sv.n_neg, sv.lse[g, c0:c1].data_ptr(),
-                         sv.ihn_num[g, c0:c1].data_ptr(), sv.ihn_imp[g, c0:c1].data_ptr(), w_tok[g, c0:c1].data_ptr(),
-                         scale.data_ptr(), float(thres), float(sv.ihn_beta), sv.n_tok_dev[g:g + 1].data_ptr(), c0, c1 - c0,
-                         gmat.data_ptr(), sv.n_neg, st)
-            else:
-                lib.call("mhr_nce_dense_bwd", s.data_ptr(), fx.data_ptr(), s.shape[1], sv.n_neg, sv.lse[g, c0:c1].data_ptr(),
-                         w_tok[g, c0:c1].data_ptr(), scale.data_ptr(), float(thres), sv.n_tok_dev[g:g + 1].data_ptr(), c0, c1 - c0,
-                         gmat.data_ptr(), sv.n_neg, st)
-            if pack is None:
+                if sv.ihn_beta > 0:
+                    lib.call("mhr_ihn_dense_bwd", s.data_ptr(), fx.data_ptr(), s.shape[1], sv.n_neg, sv.lse[g, c0:c1].data_ptr(),
+                             sv.ihn_num[g, c0:c1].data_ptr(), sv.ihn_imp[g, c0:c1].data_ptr(), w_tok[g, c0:c1].data_ptr(),
+                             scale.data_ptr(), float(thres), float(sv.ihn_beta), sv.n_tok_dev[g:g + 1].data_ptr(), c0, c1 - c0,
+                             gmat.data_ptr(), sv.n_neg, st)
+                else:
+                    lib.call("mhr_nce_dense_bwd", s.data_ptr(), fx.data_ptr(), s.shape[1], sv.n_neg, sv.lse[g, c0:c1].data_ptr(),
+                             w_tok[g, c0:c1].data_ptr(), scale.data_ptr(), float(thres), sv.n_tok_dev[g:g + 1].data_ptr(), c0, c1 - c0,
+                             gmat.data_ptr(), sv.n_neg, st)
                 del s, fx
             if pack is not None and OWN_GEMM:
                 # the two plain products on the same LDS-tiled core (mhr_wide_gemm_nt): out[r, i] = sum_k A[i, k] B[r, k]

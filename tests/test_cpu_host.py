@@ -60,6 +60,37 @@ def test_nce_fwd_has_no_switch_for_the_removed_forward_kernels():
     assert not hasattr(ops, "HOIST_FALSE_NEGATIVE_TEST")
 
 
+def test_nce_path_decision_table(monkeypatch):
+    """The one path decision of the sampled softmax (ops.nce_path), and the early prep's refusal next to it: the prepare
+    stages hand back (None, []) exactly when the call is not the row-sharing path's, or the token capacity or the negative
+    pool is not whole 32-entry tiles.  Host side only: the stages are built, never run."""
+    from mhr_amd import ops
+    monkeypatch.setattr(ops, "SHARE_ROWS", True)
+    assert ops.STREAM_DIMS == (16, 32, 64, 128, 256)
+    assert ops.nce_path(256, True, 0.0) == "shared"
+    assert ops.nce_path(256, False, 0.0) == "tokens"
+    assert ops.nce_path(64, True, 1.0) == "wide"
+    for dim in (512, 48):
+        for share in (True, False):
+            assert ops.nce_path(dim, share, 0.0) == "wide"
+
+    def stages(dim, cap, n_neg):
+        idx = torch.zeros(2, cap, dtype=torch.int32)
+        return ops.nce_shared_prepare_stages(idx, idx.clone(), torch.zeros(2, dtype=torch.int32), torch.zeros(40, dim),
+                                             torch.zeros(2, n_neg, dim, dtype=torch.bfloat16), 0.99, None, True, n_q_rows=12)
+
+    for dim in (16, 64, 256, 48, 512):
+        for cap in (64, 70):
+            for n_neg in (96, 70):
+                prep, st = stages(dim, cap, n_neg)
+                refused = ops.nce_path(dim, True, 0.0) != "shared" or cap % 32 != 0 or n_neg % 32 != 0
+                assert (prep is None and st == []) == refused, (dim, cap, n_neg)
+                assert refused or (isinstance(prep, ops.NcePrep) and len(st) == 4 and all(callable(f) for f in st))
+    monkeypatch.setattr(ops, "SHARE_ROWS", False)
+    assert ops.nce_path(256, True, 0.0) == "tokens" and ops.nce_path(512, True, 0.0) == "wide"
+    assert stages(256, 64, 96) == (None, [])
+
+
 def test_workspace_queries(built_lib):
     """The C ABI's size queries are host functions (no launch): SURVEY.md 8b - the library allocates nothing, the caller sizes
     the scorers' candidate lists from these."""

@@ -768,6 +768,62 @@ def test_nce_window_backward_without_token_atomics(ops, D, B, L, P, G, n_neg):
     assert torch.equal(dp3, dp)
 
 
+def test_nce_prep_handed_in_is_the_prep_built_inside(ops):
+    """Row-sharing forward with an early prep (ops.nce_shared_prepare, as the model builds it underneath the encoder) against the
+    same call building it inline: the forward launches are identical and atomic-free per token, so every per-token output is
+    bitwise equal (the per-offset sums are float atomics: 1e-6 relative); the backward's accumulators are the prep's, handed
+    over exactly once; a prep of other token lists is refused; ragged pools get no early prep."""
+    D, B, L, P, G, n_neg = 64, 3, 9, 4, 2, 96
+    g = torch.Generator().manual_seed(11)
+    Rq = B * G * L
+    head_rows = dev(torch.randn(Rq, D, generator=g) * 2)
+    e_rows = dev(torch.randn(B * (L + P), D, generator=g))
+    valid = torch.rand(G, B, L, P, generator=g) < 0.5
+    b_, l_, p_ = torch.arange(B)[None, :, None, None], torch.arange(L)[None, None, :, None], torch.arange(P)[None, None, None, :]
+    h_ = torch.arange(G)[:, None, None, None]
+    q_all = ((b_ * G + h_) * L + l_).expand(G, B, L, P).reshape(G, -1).int().contiguous()
+    p_all = (b_ * (L + P) + l_ + 1 + p_).expand(1, B, L, P).reshape(-1).int().contiguous()
+    o_all = p_.expand(1, B, L, P).reshape(-1).int().contiguous()
+    q_idx, p_idx, o_idx, n_tok, tos = ops.token_compact(dev(valid.reshape(G, -1)), dev(q_all), dev(p_all), dev(o_all), slot_map=True)
+    cap = q_idx.shape[1]
+    negs = bf(HO.l2n(torch.randn(G, n_neg, D, generator=g)))
+    for gi in range(G):                                   # planted false negatives, as in the test above
+        for k in range(0, int(n_tok[gi]), 4):
+            negs[gi, (k * 5) % n_neg] = bf(HO.l2n(e_rows[p_idx[gi, k].long()].cpu()[None]))[0]
+    negs = dev(negs)
+    lsd = torch.tensor([math.log(15.0)]).cuda()
+
+    def fwd(prep, q=q_idx):
+        return ops.nce_fwd(head_rows, q, e_rows, p_idx, negs, n_tok, cap, lsd, 0.99, want_logs=True, bucket_idx=o_idx, n_buckets=P,
+                           share_rows=True, window=(tos, L, P), prep=prep)
+
+    prep = ops.nce_shared_prepare(q_idx, p_idx, n_tok, e_rows, negs, 0.99, None, True, n_q_rows=Rq)
+    assert prep is not None and prep.bwd is not None
+    sv, sv0 = fwd(prep), fwd(None)
+    assert sv.shared and sv0.shared and sv.window is not None
+    for name in ("loss", "lse", "n_valid", "rank", "n_row_dev", "bucket_cnt"):
+        assert torch.equal(getattr(sv, name), getattr(sv0, name)), name
+    for gi in range(G):                                   # (s_pos is written for live tokens only: the rest of it is uninitialised)
+        assert int(n_tok[gi]) > 0 and torch.equal(sv.s_pos[gi, :int(n_tok[gi])], sv0.s_pos[gi, :int(n_tok[gi])])
+    assert bool(((sv.bucket_sum - sv0.bucket_sum).abs() <= 1e-6 * sv0.bucket_sum.abs()).all())
+    # the backward accumulates into the prep's buffers, once: the loss function takes them off the record
+    assert sv.bwd_bufs is prep.bwd and sv0.bwd_bufs is None and sv0.take_bwd_bufs() is None
+    bufs = sv.take_bwd_bufs()
+    assert bufs is prep.bwd and sv.bwd_bufs is None and sv.take_bwd_bufs() is None
+    dq, dp, dn0, dls0, lw_row = bufs
+    assert dq.shape == head_rows.shape and dp.shape == e_rows.shape
+    w_gp = dev(torch.rand(G, P, generator=g))
+    dn, dls = ops.nce_bwd(sv, w_gp, lsd, q_idx, p_idx, dq, dp, d_negs=dn0, d_logit_scale=dls0, lw_row=lw_row)
+    assert dn.data_ptr() == dn0.data_ptr() and dls.data_ptr() == dls0.data_ptr()
+    dq2, dp2 = torch.zeros_like(dq), torch.zeros_like(dp)
+    dn2, dls2 = ops.nce_bwd(sv, w_gp, lsd, q_idx, p_idx, dq2, dp2)                 # a second backward allocates fresh
+    assert dn2.data_ptr() != dn0.data_ptr() and dls2.data_ptr() != dls0.data_ptr()
+    assert torch.equal(dp2, dp)                            # (the target-row gather has no atomics)
+    with pytest.raises(ValueError, match="prep was built for other token lists"):
+        fwd(prep, q_idx.clone())
+    assert ops.nce_shared_prepare(q_idx, p_idx, n_tok, e_rows, negs[:, :70].contiguous(), 0.99, None, True, n_q_rows=Rq) is None
+
+
 @pytest.mark.parametrize("rows,cols", [(16, 1024 * 256), (25600, 256), (3, 64), (1, 8), (4097, 1032)])
 def test_sum_rows_into(ops, rows, cols):
     """Split-K partial / bias-gradient reduction into an fp32 accumulator: exact fp32 sums of the bf16 inputs up to the
