@@ -4,6 +4,7 @@ PyTorch is plumbing here: device memory (`Tensor.data_ptr()`), the current HIP s
 `torch.distributed`.  Every function enqueues hand-written gfx950 kernels from libmhr_hip.so on the
 current stream; none of them synchronises, and none has a CPU or eager fallback.
 """
+import collections
 import os
 import types
 
@@ -1326,88 +1327,133 @@ def sub_history(hist_ptr, hist_items, users_f):
     return sub_ptr, hist_items[torch.repeat_interleave(starts, lens) + off].contiguous()
 
 
-def catalog_topk(users, H, items, tag_bits, row_bits, hist_ptr, hist_items, k, cap=4096, target=None, stats=None, n_items=None,
-                 k_min=None, tau_out=None, margin=None, defer_check=None):
-    """Exact per-row top-k over the whole catalog (value desc, index asc), rows = (user, head) pairs.
+TopkPlan = collections.namedtuple("TopkPlan", "k k_min target s1 s2 t1 t2")
+TopkResult = collections.namedtuple("TopkResult", "values indices tau flagged")       # tau None: the scorer reports no threshold
+# The scorer of one call (decode_path names it; built by stream_scorer, wide.mfma_scorer or wide.gemm_scorer), as topk_decode uses it:
+# all_candidates() -> (values, indices) where the catalog is small enough to keep every score, else None; candidates() -> (tau
+# [rows], candidate lists above it in topk_select_sliced's form); exact_rows(rows, sub_ptr, sub_items) -> (values, indices), the
+# path's own repair of the rows `rows`; k_flag: the candidates a row needs; reports_tau: whether its tau certifies anything
+Scorer = collections.namedtuple("Scorer", "all_candidates candidates exact_rows k_flag reports_tau")
 
-    k_min (default k): rows with fewer than k_min candidates are re-run exactly; with k_min < k a row may return fewer than
-    k finite entries (its list then holds EVERY item scoring >= its threshold).  tau_out (dict, optional): receives 'tau'
-    [rows] f32, the emit threshold each row's candidates were collected with (-inf: every admissible item was a candidate).
 
-    users [B*H, D] bf16 normalised, items [>= N, D] bf16 normalised (rows beyond n_items = N are padding: give the
-    table round_up(N, 32) rows and the item tiles stream unclamped).  Returns (values [B*H,k] f32, indices [B*H,k] i64).
-    Thresholds come from two strided sample passes; the full pass emits the few scores above them into per-(row, item
-    slice) lists and an exact select picks the top k.  Exactness is verified (enough candidates, no list overflow, per
-    row) and rows that fail are re-run with tau = -inf, so the sampling only affects speed.
-    defer_check (int32 device tensor [>= 1], optional): instead of reading the verification flag here (a host sync) and repairing,
-    write "some row failed" into defer_check[0] and return; the caller reads it together with its own flags and, when set,
-    calls again without defer_check (catalog_topk_exact does).
-    """
-    n_rows, D = users.shape
-    N = items.shape[0] if n_items is None else int(n_items)
-    dev = users.device
-    if D not in STREAM_DIMS:
-        from . import wide
-        return wide.catalog_topk_wide(users, H, items, N, tag_bits, row_bits, hist_ptr, hist_items, k, target=target, stats=stats,
-                                      k_min=k_min, tau_out=tau_out, margin=margin)
-    ninf = torch.full((n_rows,), float("-inf"), dtype=torch.float32, device=dev)
+def topk_plan(N, k, k_min=None, target=None):
+    """The threshold budget of one decode, plain ints: a row needs k_min (<= k) candidates, `target` are aimed at; sample pass i
+    scores every s_i-th item and hands on its t_i-th largest score."""
     k_min = k if k_min is None else min(k, k_min)
-    if N <= cap:
-        cand = catalog_emit(users, H, items, tag_bits, row_bits, ninf, hist_ptr, hist_items, N, n_items=N)
-        ov, oi, _, _ = topk_select(cand, N, k)
-        if tau_out is not None:
-            tau_out["tau"] = ninf
-        return ov, oi
     if target is None:
         # candidates aimed at per row.  The threshold is the (target/s2)-th largest of a 1/s2 sample: its rank estimate
         # scatters by about 1/sqrt(target/s2), so 2.5 k leaves > 5 sigma before a row would come up short (and such a
         # row is only re-run, never wrong); every candidate above what is needed costs a divergent slow-path visit.
         target = max(512, int(2.5 * k_min))
     s1 = max(1, -(-N // 2048))
-    s2 = max(1, min(-(-N // 32768), target // 48))       # threshold = the ~50th largest of the second sample (see wide.py)
+    # second sample: dense enough that the threshold is the ~50th largest of the sample (its rank estimate then scatters by
+    # ~14 %: a row comes up short of k candidates at > 4 sigma; at N = 2^20 a 1 / 32 sample left 2.4 sigma and flagged rows -
+    # each an exact re-run - in most batches)
+    s2 = max(1, min(-(-N // 32768), target // 48))
     t1 = min(1024, max(8, -(-3 * target // s1)))           # first threshold: about 3x looser than the rank aimed at (a tighter one
-                                                   # starves the second sample and, as the fallback threshold, the candidates)
-    t2 = min(1024, max(k_min // s2 + 1, target // s2))
-    # pass 1: every s1-th item, all scores -> the t1-th largest bounds the top ~0.4 %
-    nt1 = -(-(-(-N // s1)) // 32)                                      # tiles of the first sample
-    c1 = catalog_emit_sliced(users, items, N, tag_bits, row_bits, ninf, 32 * -(-nt1 // _slices_for(n_rows, nt1)), 0, s1)
-    _, _, kth1, _, st1 = topk_select_sliced(c1, H, hist_ptr, hist_items, t1)
+                                                           # starves the second sample and, as the fallback threshold, the candidates)
+    t2 = min(1024, max(k_min // s2 + 1, target // s2))     # (the select kernel picks at most 1024)
+    return TopkPlan(k, k_min, target, s1, s2, t1, t2)
+
+
+def decode_path(D, users_dtype, items_dtype):
+    """The scorer of a catalog decode: "stream" (register-stationary, csrc/catalog.hip) at its feature dims; "mfma" (LDS-tiled,
+    csrc/catalog_wide.hip) for bf16 operands at any other multiple of 64; else "gemm" (library GEMM + csrc/wide.hip)."""
+    if D in STREAM_DIMS:
+        return "stream"
+    return "mfma" if D % 64 == 0 and users_dtype == items_dtype == torch.bfloat16 else "gemm"
+
+
+def _ninf(rows):
+    return torch.full((rows.shape[0],), float("-inf"), dtype=torch.float32, device=rows.device)
+
+
+def sampled_tau(emit, cap1, cap2, plan, H, hist_ptr, hist_items):
+    """Threshold of the stream and the MFMA scorer: two strided sample passes through the scorer's own emit(tau, cap_s, sample)
+    (sample 0: every item, 1 / 2: every s1-th / s2-th), list capacities cap1 / cap2 -> (tau, pass 2's sorted values, st1, st2)."""
+    # pass 1: every s1-th item, all scores (<= 2048 per row) -> the t1-th largest bounds the top ~0.4 %
+    _, _, kth1, _, st1 = topk_select_sliced(emit(None, cap1, 1), H, hist_ptr, hist_items, plan.t1)
     # pass 2: every s2-th item above kth1 -> the t2-th largest estimates the score of rank ~target
-    c2 = catalog_emit_sliced(users, items, N, tag_bits, row_bits, kth1, 32, 0, s2)
-    _, _, kth2, _, st2 = topk_select_sliced(c2, H, hist_ptr, hist_items, t2)
-    tau = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    lib.call("mhr_topk_pick_tau", kth1.data_ptr(), kth2.data_ptr(), st1.data_ptr(), st2.data_ptr(), n_rows, tau.data_ptr(), _stream())
-    n_sl = _slices_for(n_rows, -(-N // 32))
-    cap_s = max(32, 4 * -(-target // n_sl) + 16)
-    cand = catalog_emit_sliced(users, items, N, tag_bits, row_bits, tau, cap_s)
+    ov2, _, kth2, _, st2 = topk_select_sliced(emit(kth1, cap2, 2), H, hist_ptr, hist_items, plan.t2)
+    tau = torch.empty_like(kth1)
+    lib.call("mhr_topk_pick_tau", kth1.data_ptr(), kth2.data_ptr(), st1.data_ptr(), st2.data_ptr(), tau.shape[0], tau.data_ptr(), _stream())
+    return tau, ov2, st1, st2
+
+
+def stream_scorer(users, H, items, N, tag_bits, row_bits, hist_ptr, hist_items, plan, cap):
+    """Feature dims of STREAM_DIMS: the sliced emit; catalogs of at most `cap` items and the repair go through the atomic-list
+    emit with tau = -inf (every admissible score kept) + the whole-row select."""
+    n_rows = users.shape[0]
+    def emit(tau, cap_s, sample=0):
+        return catalog_emit_sliced(users, items, N, tag_bits, row_bits, _ninf(users) if tau is None else tau, cap_s, 0,
+                                   (1, plan.s1, plan.s2)[sample])
+
+    def every_score(rows, ptr, hist):
+        u, bits = (users, row_bits) if rows is None else (users[rows].contiguous(), row_bits[rows].contiguous())
+        return topk_select(catalog_emit(u, H, items, tag_bits, bits, _ninf(u), ptr, hist, N, n_items=N), N, plan.k)[:2]
+
+    def candidates():
+        nt1 = -(-(-(-N // plan.s1)) // 32)                                 # tiles of the first sample
+        tau = sampled_tau(emit, 32 * -(-nt1 // _slices_for(n_rows, nt1)), 32, plan, H, hist_ptr, hist_items)[0]
+        return tau, emit(tau, max(32, 4 * -(-plan.target // _slices_for(n_rows, -(-N // 32))) + 16))
+
+    return Scorer(lambda: every_score(None, hist_ptr, hist_items) if N <= cap else None, candidates, every_score, plan.k_min, True)
+
+
+def topk_decode(sc, H, row_bits, hist_ptr, hist_items, k, stats=None, defer_check=None):
+    """The decode scheme, once, for whichever Scorer it is handed: a small catalog keeps every score; otherwise per-row thresholds,
+    one full pass into candidate lists, the exact select, a flag on every row that cannot be trusted (list overflow, fewer than
+    k_flag candidates) and - after the call's one host read - the exact re-run of the flagged users' rows.  -> TopkResult."""
+    n_rows, dev = row_bits.shape[0], row_bits.device
+    small = sc.all_candidates()
+    if small is not None:
+        return TopkResult(*small, _ninf(row_bits) if sc.reports_tau else None, None)
+    tau, cand = sc.candidates()
     ov, oi, _, cnt, st = topk_select_sliced(cand, H, hist_ptr, hist_items, k)
     flagged = torch.empty(n_rows, dtype=torch.bool, device=dev)
     any_flag = defer_check if defer_check is not None else torch.empty(1, dtype=torch.int32, device=dev)
-    lib.call("mhr_topk_flag", st.data_ptr(), cnt.data_ptr(), row_bits.data_ptr(), tau.data_ptr(), int(k_min), n_rows,
+    lib.call("mhr_topk_flag", st.data_ptr(), cnt.data_ptr(), row_bits.data_ptr(), tau.data_ptr(), int(sc.k_flag), n_rows,
              flagged.data_ptr(), any_flag.data_ptr(), _stream())
     if stats is not None:
         stats["mean_candidates"] = float(cnt.float().mean())
         stats["flagged_rows"] = int(flagged.sum())
-    if defer_check is not None:                           # the caller reads the flag (with its own) and comes back if it is set
-        if tau_out is not None:
-            tau_out["tau"] = tau
-        return ov, oi
-    if bool(any_flag.item()):                             # one host sync per batch; results go to the host anyway
+    if defer_check is None and bool(any_flag.item()):     # one host sync per batch (defer_check: the caller's, with its own flags)
         users_f = torch.nonzero(flagged.view(-1, H).any(dim=1)).flatten()
         rows_f = (users_f[:, None] * H + torch.arange(H, device=dev)[None, :]).flatten()
-        sub_ptr, sub_items = sub_history(hist_ptr, hist_items, users_f)
-        sub_users = users[rows_f].contiguous()
-        sub_bits = row_bits[rows_f].contiguous()
-        sub_tau = torch.full((rows_f.numel(),), float("-inf"), dtype=torch.float32, device=dev)
-        c3 = catalog_emit(sub_users, H, items, tag_bits, sub_bits, sub_tau, sub_ptr, sub_items, N, n_items=N)
-        fv, fi, _, _ = topk_select(c3, N, k)
-        ov[rows_f] = fv
-        oi[rows_f] = fi
-        tau = tau.clone()
-        tau[rows_f] = float("-inf")
-    if tau_out is not None:
-        tau_out["tau"] = tau
-    return ov, oi
+        ov[rows_f], oi[rows_f] = sc.exact_rows(rows_f, *sub_history(hist_ptr, hist_items, users_f))
+        tau = tau.index_fill(0, rows_f, float("-inf"))
+    return TopkResult(ov, oi, tau if sc.reports_tau else None, flagged)
+
+
+def catalog_decode(users, H, items, tag_bits, row_bits, hist_ptr, hist_items, k, cap=4096, target=None, stats=None, n_items=None,
+                   k_min=None, margin=None, defer_check=None, chunk=None):
+    """Exact per-row top-k over the whole catalog (value desc, index asc), rows = (user, head) pairs: the scorer decode_path names,
+    budgeted by topk_plan, under topk_decode -> TopkResult (values [B*H,k] f32, indices [B*H,k] i64, tau [B*H] f32: the emit
+    threshold each row's candidates were collected with; -inf: every admissible item was a candidate).
+    users [B*H, D] bf16 normalised, items [>= N, D] bf16 normalised (rows beyond n_items = N are padding: give the
+    table round_up(N, 32) rows and the item tiles stream unclamped).  cap / chunk: the stream / GEMM scorer's own sizes.
+    k_min (default k): rows with fewer than k_min candidates are re-run exactly; with k_min < k a row may return fewer than
+    k finite entries (its list then holds EVERY item scoring >= its threshold).
+    margin: the caller re-ranks everything within `margin` of the k_min-th score; only the MFMA scorer's threshold needs it.
+    defer_check (int32 device tensor [>= 1]; the stream scorer only): write "some row failed" into defer_check[0] and return,
+    instead of reading it here (a host sync) and repairing; the caller reads it with its own flags and comes back (catalog_topk_exact)."""
+    from . import wide
+    N = items.shape[0] if n_items is None else int(n_items)
+    path, operands = decode_path(users.shape[1], users.dtype, items.dtype), (users, H, items, N, tag_bits, row_bits, hist_ptr, hist_items)
+    if path == "stream":
+        sc = stream_scorer(*operands, topk_plan(N, k, k_min, target), cap)
+    elif path == "mfma":
+        sc = wide.mfma_scorer(*operands, topk_plan(N, k, k_min, target), margin)
+    else:
+        sc = wide.gemm_scorer(*operands, k, target, chunk or wide.ITEM_CHUNK)
+    return topk_decode(sc, H, row_bits, hist_ptr, hist_items, k, stats, defer_check if path == "stream" else None)
+
+
+def catalog_topk(users, H, items, tag_bits, row_bits, hist_ptr, hist_items, k, cap=4096, target=None, stats=None, n_items=None,
+                 k_min=None, margin=None, defer_check=None):
+    """catalog_decode -> (values, indices)."""
+    return catalog_decode(users, H, items, tag_bits, row_bits, hist_ptr, hist_items, k, cap, target, stats, n_items, k_min, margin,
+                          defer_check)[:2]
 
 
 DENSE_ROWS_CHUNK = 128     # rows scored densely per launch (128 x 454 k x 8 B = 465 MB of scratch at cfg1)
@@ -1473,20 +1519,19 @@ def catalog_topk_exact(users_f32, H, items_bf, items_f32, tag_bits, row_bits, hi
     # ONE host read per call: the bf16 pass leaves its "some row failed" flag on the device (defer_check) next to this function's
     # "some row is uncertified" flag; only when the first is set - thresholds that came up short, never seen on trained or random
     # embeddings - the pass is repeated with its own check-and-repair
-    deferred = D in STREAM_DIMS and N > 4096 and stats is None
+    deferred = decode_path(D, users_bf.dtype, items_bf.dtype) == "stream" and N > 4096 and stats is None
     flags = torch.empty(2, dtype=torch.int32, device=dev)
     kk = min(k, k2)
     _chk(users_f32, "users_f32", torch.float32)
     _chk(items_f32, "items_f32", torch.float32)
 
     def attempt(defer):
-        tinfo = {}
-        bv, bi = catalog_topk(users_bf, H, items_bf, tag_bits, row_bits, hist_ptr, hist_items, k2, stats=stats, n_items=N, k_min=k,
-                              tau_out=tinfo, margin=2 * BF16_SCORE_ERR,      # (margin: used by the wide scorer's threshold, see wide.py)
-                              defer_check=flags[0:1] if defer else None, target=target)
-        tau = tinfo.get("tau")
-        if tau is None:               # a scorer that does not report its threshold certifies nothing: +inf flags every row
-            tau = torch.full((n_rows,), float("inf"), dtype=torch.float32, device=dev)   # (exact scorers report tau = -inf)
+        bv, bi, tau, _ = catalog_decode(users_bf, H, items_bf, tag_bits, row_bits, hist_ptr, hist_items, k2, stats=stats, n_items=N,
+                                        k_min=k, margin=2 * BF16_SCORE_ERR, defer_check=flags[0:1] if defer else None, target=target)
+        if tau is None:
+            # the GEMM scorer (its small-catalog form too) reports no threshold, which certifies nothing: +inf flags every row and
+            # all of them take the dense fp32 repair below (the other scorers' small-catalog forms report tau = -inf)
+            tau = torch.full((n_rows,), float("inf"), dtype=torch.float32, device=dev)
         bv = bv.contiguous()
         cnt = torch.empty(n_rows, dtype=torch.int32, device=dev)          # the margin set: a prefix of the sorted list
         lib.call("mhr_topk_margin_count", bv.data_ptr(), n_rows, k2, kk, 2 * BF16_SCORE_ERR, cnt.data_ptr(), _stream())

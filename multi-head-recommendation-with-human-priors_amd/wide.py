@@ -1,26 +1,27 @@
 """Wide-feature path of the sampled softmax and the catalog decode: feature dims the streaming kernels do not cover.
 
 The row-stationary HIP kernels (csrc/nce.hip, csrc/catalog.hip) keep one operand of the logit GEMM in registers, which
-bounds the feature dim at 256 (cfg0 / cfg1).  cfg2 (HSTU size-4, D = 1024) and the HLLM twin (D = 1536 / 2048)
-have contractions deep enough for the library GEMM to be the right tool: the logits are produced by
-bf16 x bf16 -> fp32 hipBLASLt GEMMs over token / item chunks (exact fp32 products of the bf16-rounded operands, fp32
-accumulation: the parity contract of the fused kernels), and everything after the GEMM is ONE hand-written pass over
-the fp32 chunk (csrc/wide.hip: loss / lse / log counters; the bf16 softmax-gradient tile; catalog masks + threshold
-emit into the candidate lists of the shared exact select) - never the reference's [N_tok, n_neg] / [B, H, N] tensor chains.
-Same interfaces and saved state as the fused path (ops.NceSaved), same parity tests; selected by ops.nce_fwd /
-ops.nce_bwd / ops.catalog_topk from the feature dim alone and NOT a fallback for a missing library (everything here
-calls into libmhr_hip.so).  One host sync per training step: the live-token count bounds the chunk loop (the
-reference syncs per prior head, hstu.py:815-816); the streaming path has none.
+bounds the feature dim at 256 (cfg0 / cfg1).  cfg2 (HSTU size-4, D = 1024) and the HLLM twin (D = 1536 / 2048):
+bf16 operands at a multiple of 64 go through the hand-written LDS-tiled MFMA contraction on packed tile images, the loss
+arithmetic (csrc/nce_wide.hip) or the catalog masks + threshold emit (csrc/catalog_wide.hip) in its epilogue - no logit or
+score block in memory.  Every other width or dtype (and REMI's loss): bf16 x bf16 -> fp32 hipBLASLt GEMMs over token / item
+chunks (exact fp32 products of the bf16-rounded operands, fp32 accumulation: the parity contract of the fused kernels) and
+ONE hand-written pass over each fp32 chunk (csrc/wide.hip) - never the reference's [N_tok, n_neg] / [B, H, N] tensor chains.
+Same interfaces and saved state as the fused path (ops.NceSaved), same parity tests; selected by ops.nce_path /
+ops.decode_path alone and NOT a fallback for a missing library (everything here calls into libmhr_hip.so).  The decode
+here is two scorers (mfma_scorer, gemm_scorer) for the one scheme in ops.topk_decode.  One host sync per training step: the
+live-token count bounds the chunk loop (the reference syncs per prior head, hstu.py:815-816); the streaming path has none.
 
 Reference: model/IDNet/hstu.py:600-629 (nce_loss, logs), 697/833 (cross entropy), 965-1015 + trainer.py:724-726 +
 collector.py:245 (scores, masks, per-head top-k).
 """
+import functools
 import math
 import os
 
 import torch
 
-from . import lib
+from . import lib, ops
 
 _PACKED = None        # (key, packed catalog, packed threshold samples) of the last catalog the wide scorer saw
 CHUNK = 8192          # tokens per logit block: 8192 x 8192 fp32 = 256 MB (x2: negatives and false-negative logits)
@@ -78,7 +79,6 @@ def _pad_rows(x, t_pad):
 def nce_fwd_wide(sv, q_rows, p_rows, logit_scale, want_logs, ihn_beta, loss, n_valid, rank):
     """sv: the common fields of the record as ops.nce_fwd prepared them (lse, s_pos and the bucket sums are filled here);
     loss / n_valid / rank [G, cap]: filled in place.  Returns the ops.NceSavedWide record."""
-    from . import ops
     G, cap, thres, negs, D, dev = sv.groups, sv.cap, sv.thres, sv.negs, sv.dim, sv.negs.device
     ihn_num, ihn_imp = (torch.zeros(G, cap, dtype=torch.float32, device=dev) for _ in range(2)) if ihn_beta > 0 else (None, None)
     qn_all, pn_all = (torch.empty(G, cap, D, dtype=torch.bfloat16, device=dev) for _ in range(2))
@@ -155,7 +155,6 @@ def nce_bwd_wide(sv, w_tok, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale
     dls = torch.zeros((), dtype=torch.float32, device=dev)
     st = _stream()
     w_tok = w_tok.contiguous()
-    from . import ops
     for g in range(G):
         ng = sv.negs[g, :sv.n_neg]
         ngt = ng.t()
@@ -231,150 +230,105 @@ def nce_bwd_wide(sv, w_tok, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale
 # ------------------------------------------------------------------------------------------------
 # catalog decode
 # ------------------------------------------------------------------------------------------------
-def _exact_rows(users, H, items, n_items, tag_bits, row_bits, hist_ptr, hist_items, k, chunk):
-    """Exact per-row top-k (value desc, index asc) with every score kept: the dense row scorer (csrc/catalog_dense.hip: fp32
-    accumulation of the operands as given, masks in place) + the exact select over the whole row.  Small catalogs and the
-    rows the threshold pass could not certify.  hist_ptr / hist_items: the CSR history of THESE users (rows // H)."""
-    from . import ops
-    rows = torch.arange(users.shape[0], dtype=torch.int32, device=users.device)
-    return ops.dense_rows_topk(users.contiguous(), H, items if items.is_contiguous() else items.contiguous(), n_items, tag_bits,
-                               row_bits, hist_ptr, hist_items, rows, k)
+def _exact_rows(users, H, items, N, tag_bits, row_bits, k, rows, hist_ptr, hist_items):
+    """Exact per-row top-k (value desc, index asc) with every score kept, of every row (rows None: small catalogs) or of `rows`
+    (those the threshold pass could not certify): the dense row scorer (csrc/catalog_dense.hip: fp32 accumulation of the operands
+    as given, masks in place) + the exact select over the whole row.  hist_ptr / hist_items: the CSR history of THESE rows' users."""
+    if rows is not None:
+        users, row_bits = users[rows], row_bits[rows].contiguous()
+    every = torch.arange(users.shape[0], dtype=torch.int32, device=users.device)
+    return ops.dense_rows_topk(users.contiguous(), H, items if items.is_contiguous() else items.contiguous(), N, tag_bits, row_bits,
+                               hist_ptr, hist_items, every, k)
 
 
-def _catalog_topk_mfma(users, H, items, N, tag_bits, row_bits, hist_ptr, hist_items, k, chunk, target, stats, k_min=None, tau_out=None,
-                       margin=None):
-    """Exact per-row top-k with the hand-written wide scorer (csrc/catalog_wide.hip: LDS-tiled MFMA GEMM, threshold emit in
-    the epilogue - no score block in memory, no library GEMM).  Same scheme as the register-stationary path
-    (ops.catalog_topk): thresholds from two strided sample passes through the SAME kernel, one full pass, the shared exact
-    select; rows that cannot be certified (list overflow, too few candidates) are re-run keeping every score."""
-    from . import lib, ops
+def mfma_scorer(users, H, items, N, tag_bits, row_bits, hist_ptr, hist_items, plan, margin):
+    """The hand-written wide scorer (csrc/catalog_wide.hip: LDS-tiled MFMA GEMM, threshold emit in the epilogue - no score block
+    in memory, no library GEMM) on packed tile images; thresholds from the two sample passes through the SAME kernel.  The one
+    scorer whose threshold needs `margin` (ops.catalog_decode)."""
     n_rows, D = users.shape
-    dev = users.device
     users, items = users.contiguous(), items.contiguous()
-    tb = None if tag_bits is None else tag_bits
-    ninf = torch.full((n_rows,), float("-inf"), dtype=torch.float32, device=dev)
     users_p = ops.pack_tiles(users, tiles_per_block=4)                              # once per batch (a few MB)
     SEL = 8192                                                                    # candidates the select kernel holds per row
-    k_min = k if k_min is None else min(k, k_min)
-    if target is None:
-        target = max(512, int(2.5 * k_min))
-    s1 = max(1, -(-N // 2048))
-    # second sample: dense enough that the threshold is the ~50th largest of the sample (its rank estimate then scatters by
-    # ~14 %: a row comes up short of k candidates at > 4 sigma; at N = 2^20 a 1 / 32 sample left 2.4 sigma and flagged rows -
-    # each an exact re-run - in most batches)
-    s2 = max(1, min(-(-N // 32768), target // 48))
     # the catalog's packed images (whole, and the two strided samples of the threshold passes) depend on the table only:
     # built once per cached catalog (the evaluation normalises and caches it, REC/model/multihead.py:_normalised_items)
     # (keyed on the tensor OBJECT, which the cache keeps alive: an address alone may be a freed table's, reused)
     global _PACKED
-    if _PACKED is None or _PACKED[0] is not items or _PACKED[1] != (items._version, N, s1, s2):
-        full = ops.pack_tiles(items, n_sel=N)
-        samp = None if N <= SEL else (ops.pack_tiles(items[:N], row_stride=s1), ops.pack_tiles(items[:N], row_stride=s2))
-        _PACKED = (items, (items._version, N, s1, s2), full, samp)
-    items_p, samples = _PACKED[2], _PACKED[3]
-    if N <= SEL:                                                                   # small catalogs: every score is a candidate
-        cand = ops.catalog_emit_wide(users_p, n_rows, D, items_p, N, tb, row_bits, ninf, 64)     # >= 32 slices: one block per slice at most
-        ov, oi, _, _, _ = ops.topk_select_sliced(cand, H, hist_ptr, hist_items, k)
-        if tau_out is not None:
-            tau_out["tau"] = ninf
-        return ov, oi
-    t1 = min(1024, max(8, -(-3 * target // s1)))           # first threshold: about 3x looser than the rank aimed at (a tighter one
-                                                   # starves the second sample and, as the fallback threshold, the candidates)
-    t2 = min(max(k_min // s2 + 1, target // s2), 1024)             # (the select kernel picks at most 1024)
-    # pass 1: every s1-th item, all scores (<= 2048 per row, <= 64 per list) -> the t1-th largest bounds the top ~0.4 %
-    c1 = ops.catalog_emit_wide(users_p, n_rows, D, samples[0], N, tb, row_bits, ninf, 64, 0, s1)
-    _, _, kth1, _, st1 = ops.topk_select_sliced(c1, H, hist_ptr, hist_items, t1)
-    # pass 2: every s2-th item above kth1 -> the t2-th largest estimates the score of rank ~target
-    c2 = ops.catalog_emit_wide(users_p, n_rows, D, samples[1], N, tb, row_bits, kth1, 32, 0, s2)
-    ov2, _, kth2, _, st2 = ops.topk_select_sliced(c2, H, hist_ptr, hist_items, t2)
-    ok2 = (st2 == 0) & (st1 == 0)
-    tau = torch.where(torch.isfinite(kth2) & ok2, kth2, torch.where(ok2, kth1, ninf)).contiguous()
-    if margin is not None:
-        # the caller re-ranks everything within `margin` of the k_min-th score (ops.catalog_topk_exact): the threshold must lie
-        # below that band, however many items it holds - with (near-)random embeddings at wide feature dims the cosines
-        # concentrate (std 1 / sqrt(D)) and the band holds several hundred.  The k_min-th score is estimated from the second
-        # sample (rank k_min / s2, taken two standard deviations of its rank noise further down).
-        r_k = k_min // s2 + 1
-        r_lo = min(t2 - 1, r_k + int(2.0 * r_k ** 0.5) + 1)
-        est = ov2[:, r_lo]
-        tau_m = torch.where(torch.isfinite(est) & ok2, est - margin, tau)
-        tau = torch.minimum(tau, tau_m).contiguous()
-        target = max(target, 4096)                   # list capacity for the band (candidates per row the lists can hold)
-    n_sl = lib.load().mhr_catalog_wide_slices(n_rows)
-    cap_s = max(32, 4 * -(-target // (4 * n_sl)) + 16)
-    cand = ops.catalog_emit_wide(users_p, n_rows, D, items_p, N, tb, row_bits, tau, cap_s)
-    ov, oi, _, got, stt = ops.topk_select_sliced(cand, H, hist_ptr, hist_items, k)
-    flagged = (stt != 0) | ((got < k_min) & (row_bits != 0) & torch.isfinite(tau))
-    if stats is not None:
-        stats["mean_candidates"] = float(got.float().mean())
-        stats["flagged_rows"] = int(flagged.sum())
-    if bool(flagged.any()):                               # one host sync per batch; results go to the host anyway
-        users_f = torch.nonzero(flagged.view(-1, H).any(dim=1)).flatten()
-        rows_f = (users_f[:, None] * H + torch.arange(H, device=dev)[None, :]).flatten()
-        sub_ptr, sub_items = ops.sub_history(hist_ptr, hist_items, users_f)
-        fv, fi = _exact_rows(users[rows_f].contiguous(), H, items, N, tag_bits, row_bits[rows_f].contiguous(), sub_ptr, sub_items,
-                             k, chunk)
-        ov[rows_f] = fv
-        oi[rows_f] = fi
-        tau = tau.clone()
-        tau[rows_f] = float("-inf")
-    if tau_out is not None:
-        tau_out["tau"] = tau
-    return ov, oi
+    key = (items._version, N, plan.s1, plan.s2)
+    if _PACKED is None or _PACKED[0] is not items or _PACKED[1] != key:
+        images = [ops.pack_tiles(items, n_sel=N)]
+        images += [] if N <= SEL else [ops.pack_tiles(items[:N], row_stride=s) for s in (plan.s1, plan.s2)]
+        _PACKED = (items, key, images)
+    images = _PACKED[2]
+
+    def emit(tau, cap_s, sample=0):
+        return ops.catalog_emit_wide(users_p, n_rows, D, images[sample], N, tag_bits, row_bits, ops._ninf(users) if tau is None else tau,
+                                     cap_s, 0, (1, plan.s1, plan.s2)[sample])
+
+    def all_candidates():
+        if N <= SEL:                                                              # (>= 32 slices: one block per slice at most)
+            return ops.topk_select_sliced(emit(None, 64), H, hist_ptr, hist_items, plan.k)[:2]
+
+    def candidates():
+        tau, ov2, st1, st2 = ops.sampled_tau(emit, 64, 32, plan, H, hist_ptr, hist_items)        # (pass 1: <= 64 scores per list)
+        budget = plan.target if margin is None else max(plan.target, 4096)   # (4096: list capacity, candidates per row, for the band)
+        if margin is not None:
+            # the caller re-ranks everything within `margin` of the k_min-th score (ops.catalog_topk_exact): the threshold must lie
+            # below that band, however many items it holds - with (near-)random embeddings at wide feature dims the cosines
+            # concentrate (std 1 / sqrt(D)) and the band holds several hundred.  The k_min-th score is estimated from the second
+            # sample (rank k_min / s2, taken two standard deviations of its rank noise further down).
+            r_k = plan.k_min // plan.s2 + 1
+            est = ov2[:, min(plan.t2 - 1, r_k + int(2.0 * r_k ** 0.5) + 1)]
+            tau_m = torch.where(torch.isfinite(est) & (st2 == 0) & (st1 == 0), est - margin, tau)
+            tau = torch.minimum(tau, tau_m).contiguous()
+        n_sl = lib.load().mhr_catalog_wide_slices(n_rows)
+        return tau, emit(tau, max(32, 4 * -(-budget // (4 * n_sl)) + 16))
+
+    exact_rows = functools.partial(_exact_rows, users, H, items, N, tag_bits, row_bits, plan.k)
+    return ops.Scorer(all_candidates, candidates, exact_rows, plan.k_min, True)
+
+
+def gemm_scorer(users, H, items, N, tag_bits, row_bits, hist_ptr, hist_items, k, target, chunk):
+    """Every other width or dtype: scores of item chunks from the library GEMM, masks and threshold emit in one pass over each
+    fp32 chunk (csrc/wide.hip).  Its own budget: one sample at a floor stride, the default target from k, rows need k candidates.
+    Reports no threshold."""
+    n_rows, dev, st = users.shape[0], users.device, _stream()
+    tagp = 0 if tag_bits is None else tag_bits.data_ptr()
+    target = max(512, int(2.5 * k)) if target is None else target
+    exact_rows = functools.partial(_exact_rows, users, H, items, N, tag_bits, row_bits, k)
+
+    def all_candidates():
+        if N <= max(4 * k, 2048) or N <= chunk // 8:
+            return exact_rows(None, hist_ptr, hist_items)
+
+    def candidates():
+        # threshold: the score of rank ~target, estimated on every s-th item
+        s = max(1, N // 32768)
+        t = max(k // s + 1, target // s)
+        sample = items[0:N:s].contiguous()
+        sc = _mm(users, sample.t())
+        lib.call("mhr_catalog_mask_dense", sc.data_ptr(), sc.shape[1], sample.shape[0], 0, s, tagp, row_bits.data_ptr(), n_rows, st)
+        tau = torch.topk(sc, min(t, sc.shape[1]), dim=1).values[:, -1].contiguous()                  # -inf: too few admissible -> exact
+        del sc
+        per = 8
+        seg = -(-chunk // per)
+        n_lists = -(-N // chunk) * per
+        cap_s = max(32, 4 * -(-target // n_lists) + 16)
+        val = torch.empty(n_rows, n_lists, cap_s, dtype=torch.float32, device=dev)
+        idx = torch.empty(n_rows, n_lists, cap_s, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(n_rows, n_lists, dtype=torch.int32, device=dev)
+        for ci, i0 in enumerate(range(0, N, chunk)):
+            i1 = min(N, i0 + chunk)
+            sc = _mm(users, items[i0:i1].t())
+            lib.call("mhr_catalog_emit_dense", sc.data_ptr(), sc.shape[1], i1 - i0, seg, i0, tagp, row_bits.data_ptr(), tau.data_ptr(),
+                     n_rows, val.data_ptr(), idx.data_ptr(), cnt.data_ptr(), n_lists, ci * per, cap_s, st)
+            del sc
+        return tau, (val, idx, cnt, n_lists)
+
+    return ops.Scorer(all_candidates, candidates, exact_rows, k, False)
 
 
 def catalog_topk_wide(users, H, items, n_items, tag_bits, row_bits, hist_ptr, hist_items, k, chunk=ITEM_CHUNK, target=None,
-                      stats=None, k_min=None, tau_out=None, margin=None):
-    """Exact per-row top-k over the catalog at any feature dim.  Thresholds from a strided sample of the catalog; the
-    full pass scores item chunks with the library GEMM and emits the few scores above the threshold (csrc/wide.hip) into
-    candidate lists; the exact select of the streaming path (topk_select_sliced) picks the top k with the history filter.
-    Rows it cannot certify (too few candidates, list overflow) are re-run keeping every score - sampling only affects speed."""
-    from . import ops
-    n_rows, D = users.shape
-    N = int(n_items)
-    dev = users.device
-    if D % 64 == 0 and users.dtype == torch.bfloat16 and items.dtype == torch.bfloat16:
-        return _catalog_topk_mfma(users, H, items, N, tag_bits, row_bits, hist_ptr, hist_items, k, chunk, target, stats, k_min, tau_out,
-                                  margin)
-    if N <= max(4 * k, 2048) or N <= chunk // 8:
-        return _exact_rows(users, H, items, N, tag_bits, row_bits, hist_ptr, hist_items, k, chunk)
-    st = _stream()
-    tagp = 0 if tag_bits is None else tag_bits.data_ptr()
-    if target is None:
-        target = max(512, int(2.5 * k))
-    # threshold: the score of rank ~target, estimated on every s-th item
-    s = max(1, N // 32768)
-    t = max(k // s + 1, target // s)
-    sample = items[0:N:s].contiguous()
-    sc = _mm(users, sample.t())
-    lib.call("mhr_catalog_mask_dense", sc.data_ptr(), sc.shape[1], sample.shape[0], 0, s, tagp, row_bits.data_ptr(), n_rows, st)
-    tau = torch.topk(sc, min(t, sc.shape[1]), dim=1).values[:, -1].contiguous()                  # -inf: too few admissible -> exact
-    del sc
-    n_chunks = -(-N // chunk)
-    per = 8
-    seg = -(-chunk // per)
-    n_lists = n_chunks * per
-    cap_s = max(32, 4 * -(-target // n_lists) + 16)
-    val = torch.empty(n_rows, n_lists, cap_s, dtype=torch.float32, device=dev)
-    idx = torch.empty(n_rows, n_lists, cap_s, dtype=torch.int32, device=dev)
-    cnt = torch.zeros(n_rows, n_lists, dtype=torch.int32, device=dev)
-    for ci, i0 in enumerate(range(0, N, chunk)):
-        i1 = min(N, i0 + chunk)
-        sc = _mm(users, items[i0:i1].t())
-        lib.call("mhr_catalog_emit_dense", sc.data_ptr(), sc.shape[1], i1 - i0, seg, i0, tagp, row_bits.data_ptr(), tau.data_ptr(),
-                 n_rows, val.data_ptr(), idx.data_ptr(), cnt.data_ptr(), n_lists, ci * per, cap_s, st)
-        del sc
-    ov, oi, _, got, stt = ops.topk_select_sliced((val, idx, cnt, n_lists), H, hist_ptr, hist_items, k)
-    flagged = (stt != 0) | ((got < k) & (row_bits != 0) & torch.isfinite(tau))
-    if stats is not None:
-        stats["mean_candidates"] = float(got.float().mean())
-        stats["flagged_rows"] = int(flagged.sum())
-    if bool(flagged.any()):                               # one host sync per batch; results go to the host anyway
-        users_f = torch.nonzero(flagged.view(-1, H).any(dim=1)).flatten()
-        rows_f = (users_f[:, None] * H + torch.arange(H, device=dev)[None, :]).flatten()
-        sub_ptr, sub_items = ops.sub_history(hist_ptr, hist_items, users_f)
-        fv, fi = _exact_rows(users[rows_f].contiguous(), H, items, N, tag_bits, row_bits[rows_f].contiguous(), sub_ptr, sub_items,
-                             k, chunk)
-        ov[rows_f] = fv
-        oi[rows_f] = fi
-    return ov, oi
+                      stats=None, k_min=None, margin=None):
+    """ops.catalog_decode (at any feature dim, with the GEMM scorer's item chunk) -> (values, indices)."""
+    return ops.catalog_decode(users, H, items, tag_bits, row_bits, hist_ptr, hist_items, k, target=target, stats=stats, n_items=n_items,
+                              k_min=k_min, margin=margin, chunk=chunk)[:2]

@@ -91,6 +91,40 @@ def test_nce_path_decision_table(monkeypatch):
     assert stages(256, 64, 96) == (None, [])
 
 
+@pytest.mark.parametrize("N,k,k_min,target,want", [
+    (453938, 200, None, None, (512, 222, 10, 8, 51)),
+    (453938, 464, 200, None, (512, 222, 10, 8, 51)),
+    (60000, 200, None, None, (512, 30, 2, 52, 256)),
+    (60000, 200, None, 208, (208, 30, 2, 21, 104)),
+    (1048576, 1024, 200, None, (512, 512, 10, 8, 51)),
+    (40000, 100, None, None, (512, 20, 2, 77, 256)),
+    (40000, 100, None, 20000, (20000, 20, 2, 1024, 1024)),
+    (4097, 20, None, None, (512, 3, 1, 512, 512)),
+    (9000, 1000, 1000, None, (2500, 5, 1, 1024, 1024))])
+def test_topk_plan_table(N, k, k_min, target, want):
+    """The decode's one budget (ops.topk_plan): target, the two sample strides and the two sample ranks, as the stream and the
+    MFMA scorer computed them separately before; plain ints."""
+    from mhr_amd import ops
+    plan = ops.topk_plan(N, k, k_min, target)
+    assert tuple(plan) == (k, k if k_min is None else k_min) + want
+    assert all(type(v) is int for v in plan)
+    assert (plan.k, plan.k_min, plan.target, plan.s1, plan.s2, plan.t1, plan.t2) == tuple(plan)
+
+
+def test_decode_path_decision_table():
+    """The one scorer decision of the catalog decode (ops.decode_path)."""
+    from mhr_amd import ops
+    bf16, f32 = torch.bfloat16, torch.float32
+    for dim in (16, 64, 256):
+        assert ops.decode_path(dim, bf16, bf16) == "stream"
+    for dim in (512, 1024, 320):
+        assert ops.decode_path(dim, bf16, bf16) == "mfma"
+    for dim in (96, 48):
+        assert ops.decode_path(dim, bf16, bf16) == "gemm"
+    assert ops.decode_path(512, f32, f32) == "gemm"
+    assert ops.decode_path(512, bf16, f32) == "gemm" and ops.decode_path(512, f32, bf16) == "gemm"
+
+
 def test_workspace_queries(built_lib):
     """The C ABI's size queries are host functions (no launch): SURVEY.md 8b - the library allocates nothing, the caller sizes
     the scorers' candidate lists from these."""
