@@ -615,6 +615,33 @@ int mhr_catalog_score_rows_dense(const void* users, const void* items, int dtype
                                  const uint32_t* row_bits, const int32_t* hist_ptr, const int64_t* hist_items,
                                  float* out_val, int32_t* out_idx, int32_t* out_cnt, void* stream);
 
+/* split_mode = average (evaluator/collector.py:227-230: sum of a user's FINITE head scores / (finite count + 1e-8), then
+ * torch.topk; the -inf masks are those of model/IDNet/hstu.py:982-1015 and trainer/trainer.py:724-726).  Head h is finite for
+ * item n iff n != 0, n is not in the user's history and (row_bits[b*H + h] & tag_bits[n]) != 0, so the finite set depends on n
+ * only through its tag word w and, the dot product being linear, mean(b, n) = q[b, w] . items[n] with q[b, w] = (sum of the heads
+ * live for w) / count: a single-head decode with P = (distinct tag words) query rows per user (ops.catalog_topk_mean).
+ *  head_mean_queries: q[b*P + p, :] = (sum over h ascending of heads[b, h, :] where (row_bits[b*H + h] & words[p]) != 0) / count
+ *      (heads [B, H, dim] fp32 L2-normalised, words [P] uint32 the distinct tag words, P <= 32); q_bits[b*P + p] = 1 << p
+ *      (has_tags = 0: bit 31, the word the scorers give every item without a tag table; then P = 1), or 0 with q = 0 when no head
+ *      is live - a dead row, as the scorers understand it.
+ *  rescore_mean_f32: the list format and layout of the fp32 re-score above for the candidates of row r = b*P + p, with the
+ *      reference's own arithmetic: out_val[r, j] = (sum over h ascending of heads[b, h, :] . items[n, :] where
+ *      (row_bits[b*H + h] & tag_bits[n]) != 0) / float(count), n = cand_idx[r, j], or 0 when count = 0 (count + 1e-8 == count in
+ *      fp32 for count >= 1).  tag_bits: the REAL tag words (NULL: bit 31 for every item), not the pattern words.
+ *  catalog_mean_rows_dense: for the n_list users b = user_list[j]: out_val[j, n] = that mean over the heads finite for (b, n) with
+ *      the pad id, the history (CSR over users, as above) and the tag / row bits applied, and 0.0f - NOT -inf - where no head
+ *      is finite (collector.py:228: 0 / 1e-8; such items outrank negative means); out_idx[j, n] = n, out_cnt[j] = n_items: the
+ *      list format of the exact select with cap = n_items.  Operands fp32; the H head rows sit in LDS (H <= 64, H * dim <= 16000,
+ *      dots formed for 8 heads at a time), dim % 4 == 0, out_* [n_list, n_items], n_list <= 65535. */
+int mhr_head_mean_queries(const float* heads, const uint32_t* row_bits, const uint32_t* words, int B, int H, int P, int dim,
+                          int has_tags, float* q, uint32_t* q_bits, void* stream);
+int mhr_rescore_mean_f32(const float* heads, const float* items, int dim, int64_t n_items, int H, int P, const uint32_t* tag_bits,
+                         const uint32_t* row_bits, const int64_t* cand_idx, int n_rows, int k2, const int32_t* cand_cnt,
+                         float* out_val, int32_t* out_idx, void* stream);
+int mhr_catalog_mean_rows_dense(const float* heads, const float* items, int dim, int64_t n_items, const int32_t* user_list,
+                                int n_list, int H, const uint32_t* tag_bits, const uint32_t* row_bits, const int32_t* hist_ptr,
+                                const int64_t* hist_items, float* out_val, int32_t* out_idx, int32_t* out_cnt, void* stream);
+
 /* The decode's exactness bookkeeping (ops.catalog_topk / catalog_topk_exact; replaces the masks the reference needs none of because
  * it ranks a dense [B, H, N] score tensor, hstu.py:965-1015 + collector.py:245) - one launch per decision:
  *  pick_tau:     tau[r] = kth2[r] if both sample selects were clean (status 0) and kth2 is finite, else kth1[r] if clean, else -inf.
@@ -766,12 +793,14 @@ int mhr_det_sum_into(const float* parts, int64_t n, const float* scale_dev, int 
  *   ..._emit_sliced_workspace_bytes(n_rows, n_sel_items, cap_s)   2 n_slices lists of cap_s slots per row
  *   ..._emit_wide_workspace_bytes(n_rows, cap_s)                  4 mhr_catalog_wide_slices(n_rows) lists of cap_s slots per row
  *   ..._emit_workspace_bytes(n_rows, cap)                         one list of cap slots per row
- *   ..._rows_dense_workspace_bytes(n_list, n_items)               one slot per (listed row, item) */
+ *   ..._rows_dense_workspace_bytes(n_list, n_items)               one slot per (listed row, item)
+ *   ..._mean_rows_dense_workspace_bytes(n_list, n_items)          one slot per (listed user, item) */
 int mhr_catalog_emit_slices(int n_rows, int64_t n_sel_items);
 int64_t mhr_catalog_score_emit_sliced_workspace_bytes(int n_rows, int64_t n_sel_items, int cap_s);
 int64_t mhr_catalog_score_emit_wide_workspace_bytes(int n_rows, int cap_s);
 int64_t mhr_catalog_score_emit_workspace_bytes(int n_rows, int cap);
 int64_t mhr_catalog_score_rows_dense_workspace_bytes(int n_list, int64_t n_items);
+int64_t mhr_catalog_mean_rows_dense_workspace_bytes(int n_list, int64_t n_items);
 /* Rows {row_begin + j * row_stride, j < n_sel} of x [n_rows, dim] bf16 (dim % 64 == 0) -> packed tile images
  * [ceil(n_sel / (32 tiles_per_block))][dim / 64][tiles_per_block][4096 B] (32 rows x 64 features each, XOR-swizzled like
  * the LDS tiles; rows past n_sel / n_rows are zero).  out: mhr_pack_tiles_bytes(n_sel, dim, tiles_per_block) bytes. */

@@ -77,7 +77,7 @@ class Collector(object):
     def _decode(self, scores, top_k, detail):
         """-> merged item ids [B, top_k] int64 on the device."""
         from mhr_amd import ops
-        fused = hasattr(scores, 'indices')
+        fused = not torch.is_tensor(scores)         # (every torch.Tensor has an `indices` attribute: test the type, not the name)
         if fused:
             vals, idx = scores.values, scores.indices
             if vals.shape[-1] < top_k:
@@ -99,7 +99,12 @@ class Collector(object):
                 detail['values'], detail['idx'] = vals[:, 0], idx[:, 0]
             return idx[:, 0].contiguous()
         if self.split_mode != 'combine':
-            raise ValueError(f"split_mode={self.split_mode} needs dense scores" if fused else f'Unknown split_mode: {self.split_mode}')
+            if fused and self.split_mode == 'average':
+                # the models' fused average decode hands ONE list per user ([B,1,k]: MultiHeadDecoding._decode_topk); per-head
+                # lists cannot be averaged after the fact (an item's mean needs its score in every head)
+                raise ValueError(f"split_mode=average: got per-head top-k lists [B,{H},k]; the mean over heads needs the fused "
+                                 "average decode (a FusedTopK [B,1,k]) or dense scores [B,H,N]")
+            raise ValueError(f'Unknown split_mode: {self.split_mode}')
         out_idx, out_val, out_src, status = ops.multihead_merge_dedup(vals.contiguous(), idx.contiguous(), B, H, top_k)
         if detail is not None:
             detail.update(values=out_val, head_source=out_src, idx=out_idx, values_by_head=vals, idx_by_head=idx, unique=status)

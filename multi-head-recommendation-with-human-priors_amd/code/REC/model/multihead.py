@@ -62,6 +62,9 @@ class MultiHeadDecoding:
         # evaluation ranks fp32 scores of fp32 operands like the reference (bit-exact top-k indices wherever the reference's
         # scores are untied); False: rank the bf16 MFMA scores directly (the candidates' order within 2^-8 may differ)
         self.exact_fp32_topk = bool(config.get('exact_fp32_topk', True))
+        # how the collector merges the heads (reference collector.py:203-285): 'combine' ranks per head and merges the lists,
+        # 'average' ranks the mean over each item's finite heads - the decode then hands ONE list per user (`_decode_topk`)
+        self.split_mode = config.get('split_mode', 'combine') or 'combine'
         self.seg_len = self.pred_len
         if nl > 0:
             assert self.pred_len % self.num_segment_head == 0, "pred_len must be divisible by the number of segments"
@@ -545,14 +548,27 @@ class MultiHeadDecoding:
             tag_bits = self.pack_item_tags(all_item_tags) if (all_item_tags is not None and self.loss == 'prior') else None
             # fp32 normalised rows for the exact re-score of the final candidates (the reference ranks fp32 scores)
             items_f32 = ops.l2norm_rows(feat, torch.float32) if self.exact_fp32_topk else None
-            self._item_cache = (key, items_bf, tag_bits, items_f32)
+            self._item_cache = (key, items_bf, tag_bits, items_f32, {})       # {}: what is derived from the table lazily
         return self._item_cache[1], self._item_cache[2]
+
+    def _tag_patterns(self):
+        """Distinct tag words of the catalog and the one-hot pattern word of every item (ops.tag_patterns), computed once per
+        (item table, tags): kept in the item cache of `_normalised_items` (call that first)."""
+        from mhr_amd import ops
+        extra = self._item_cache[4]
+        if "patterns" not in extra:
+            words, pattern_bits = ops.tag_patterns(self._item_cache[2])
+            extra["patterns"] = (words.to(self._item_cache[1].device), pattern_bits)       # (no tag table: built on the host)
+        return extra["patterns"]
 
     @torch.no_grad()
     def _decode_topk(self, last, all_item_feature, all_item_tags, target_tags, history, k, suppress_history, stats, n_ids,
                      heads_n=None, defer=False):
         """Heads at the last position -> catalog scoring with tag / pad / history / switch masks -> exact per-head top-k.
-        Replaces reference hstu.py:915-1015 + trainer.py:724-726 + collector.py:245 without the [B,H,N] tensor."""
+        Replaces reference hstu.py:915-1015 + trainer.py:724-726 + collector.py:245 without the [B,H,N] tensor.
+        split_mode 'average' with more than one head: the top-k of the MEAN over each item's finite heads instead (collector.py:
+        227-230), as ONE list per user - FusedTopK [B,1,k], which the collector takes as it takes a single head
+        (ops.catalog_topk_mean).  It ranks fp32 means only (`exact_fp32_topk: False` raises) and has no deferred form."""
         from mhr_amd import ops
         B = (last if heads_n is None else heads_n).shape[0]
         H = self.medusa_num_heads
@@ -577,6 +593,15 @@ class MultiHeadDecoding:
             hist_items = hi[order].contiguous()
             # CSR offsets by binary search on the sorted user column (torch.bincount would sync the host)
             hist_ptr = torch.searchsorted(hu[order].contiguous(), torch.arange(B + 1, device=dev)).int()
+        if self.split_mode == 'average' and H > 1:
+            if defer:
+                raise ValueError("deferred decode is not built for split_mode=average")
+            if not self.exact_fp32_topk:
+                raise ValueError("split_mode=average ranks fp32 means of fp32 scores: it needs exact_fp32_topk: True")
+            vals, idx = ops.catalog_topk_mean(heads_n.reshape(B, H, -1).float().contiguous(), items_bf, self._item_cache[3], tag_bits,
+                                              row_bits, hist_ptr, hist_items, k, patterns=self._tag_patterns(),
+                                              n_items=all_item_feature.shape[0], stats=stats)
+            return FusedTopK(vals.view(B, 1, k), idx.view(B, 1, k), logs)
         if self.exact_fp32_topk:
             # ranked on fp32 scores like the reference (hstu.py:965-979 + collector.py:245): bf16 scorer for the candidates
             # within 2^-7 of the k-th score, fp32 re-score of those, exact select (ops.catalog_topk_exact)

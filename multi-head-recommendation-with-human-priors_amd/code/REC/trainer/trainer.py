@@ -597,6 +597,7 @@ class Trainer(object):
                 and item_seq.is_cuda and type(m).__name__ == "HSTU" and getattr(m, "_hstu_embedding_dim", 0) in ops.STREAM_DIMS
                 and getattr(m, "exact_fp32_topk", False) and m.item_num > 4096 and not getattr(m, "prior_given_at_test", False)
                 and getattr(m, "prior_switch", None) is None and isinstance(m.item_id_proj_tower, torch.nn.Identity)
+                and not (getattr(m, "split_mode", "combine") == "average" and m.medusa_num_heads > 1)   # no deferred average decode
                 and not getattr(self, "_eval_graph_failed", None))
 
     @torch.no_grad()

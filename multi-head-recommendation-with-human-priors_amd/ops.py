@@ -1492,6 +1492,45 @@ def dense_rows_topk(users, H, items, n_items, tag_bits, row_bits, hist_ptr, hist
 BF16_SCORE_ERR = 2.0 ** -8       # |u_bf16 . i_bf16 - u . i| for unit vectors u, i (each component rounded to 8 bits)
 
 
+def _margin_slots(N, k, D):
+    """Candidates kept per row by the exact decodes: the margin set must fit.  Wide feature dims concentrate the cosines of
+    (near-)random embeddings around 0 (std 1 / sqrt(D)), so a 2^-7 margin below the k-th score holds several hundred items there:
+    keep the maximum."""
+    k2 = min(N - 1, 1024, max(2 * k + 64, k + 256) if D <= 256 else 1024)
+    return k if k2 <= k else k2
+
+
+def _exact_attempt(users_bf, H, items_bf, N, tag_bits, row_bits, hist_ptr, hist_items, k, k2, flags, defer, stats, target, rescore):
+    """One pass of the exact decodes (catalog_topk_exact, catalog_topk_mean): the bf16 scorer's candidate lists (everything above a
+    per-row threshold tau near the rank-2.5k score), the best k2 of them sorted, the margin set of every row re-scored by
+    `rescore(cand_idx [n_rows,k2] i64, cand_cnt [n_rows] i32, out_val [n_rows,k2] f32, out_idx [n_rows,k2] i32)` in fp32, the exact
+    select on the re-scored values.  A row is CERTIFIED when its margin [kth - 2^-7, ...) lies above tau (nothing that could enter
+    the fp32 top-k was left below the threshold) and does not fill all k2 slots.  flags (int32 [>= 2], device): [0] the bf16 pass's
+    "some row failed" when `defer` (else it is read and repaired inside catalog_decode), [1] "some row is uncertified".
+    -> (values [n_rows,k], indices [n_rows,k], margin counts, uncertified [n_rows] bool)."""
+    n_rows, dev = users_bf.shape[0], users_bf.device
+    kk = min(k, k2)
+    bv, bi, tau, _ = catalog_decode(users_bf, H, items_bf, tag_bits, row_bits, hist_ptr, hist_items, k2, stats=stats, n_items=N,
+                                    k_min=k, margin=2 * BF16_SCORE_ERR, defer_check=flags[0:1] if defer else None, target=target)
+    if tau is None:
+        # the GEMM scorer (its small-catalog form too) reports no threshold, which certifies nothing: +inf flags every row and
+        # all of them take the dense fp32 repair (the other scorers' small-catalog forms report tau = -inf)
+        tau = torch.full((n_rows,), float("inf"), dtype=torch.float32, device=dev)
+    bv = bv.contiguous()
+    cnt = torch.empty(n_rows, dtype=torch.int32, device=dev)          # the margin set: a prefix of the sorted list
+    lib.call("mhr_topk_margin_count", bv.data_ptr(), n_rows, k2, kk, 2 * BF16_SCORE_ERR, cnt.data_ptr(), _stream())
+    rv = torch.empty(n_rows, k2, dtype=torch.float32, device=dev)
+    ri = torch.empty(n_rows, k2, dtype=torch.int32, device=dev)
+    rescore(bi, cnt, rv, ri)
+    ov, oi, _, st = topk_select((rv, ri, cnt), k2, k)
+    # uncertified rows: the margin reaches below the emit threshold, or fills the candidate list (the (k2+1)-th bf16 score
+    # might be inside it too)
+    full = torch.empty(n_rows, dtype=torch.bool, device=dev)
+    lib.call("mhr_topk_uncertified", cnt.data_ptr(), bv.data_ptr(), k2, kk, tau.contiguous().data_ptr(), 1 if k2 < N - 1 else 0,
+             2 * BF16_SCORE_ERR, n_rows, full.data_ptr(), flags[1:2].data_ptr(), _stream())
+    return ov, oi, cnt, full
+
+
 def catalog_topk_exact(users_f32, H, items_bf, items_f32, tag_bits, row_bits, hist_ptr, hist_items, k, n_items=None, stats=None,
                        target=None, defer=False):
     """Per-row top-k ranked on FP32 scores of fp32 operands - the reference's score path (hstu.py:965-979: fp32 normalise,
@@ -1508,44 +1547,22 @@ def catalog_topk_exact(users_f32, H, items_bf, items_f32, tag_bits, row_bits, hi
     N = items_f32.shape[0] if n_items is None else int(n_items)
     dev = users_f32.device
     users_bf = users_f32.to(torch.bfloat16).contiguous()
-    # candidates kept per row: the margin set must fit.  Wide feature dims concentrate the cosines of (near-)random embeddings
-    # around 0 (std 1 / sqrt(D)), so a 2^-7 margin below the k-th score holds several hundred items there: keep the maximum
-    k2 = min(N - 1, 1024, max(2 * k + 64, k + 256) if D <= 256 else 1024)
-    if k2 <= k:
-        k2 = k
-    # the bf16 scorer's candidate lists (everything above a per-row threshold tau near the rank-2.5k score), the best k2 of them
-    # sorted; a row is CERTIFIED when its margin [kth - 2^-7, ...) lies above tau (nothing that could enter the fp32 top-k was
-    # left below the threshold) and does not fill all k2 slots
+    k2 = _margin_slots(N, k, D)
     # ONE host read per call: the bf16 pass leaves its "some row failed" flag on the device (defer_check) next to this function's
     # "some row is uncertified" flag; only when the first is set - thresholds that came up short, never seen on trained or random
     # embeddings - the pass is repeated with its own check-and-repair
     deferred = decode_path(D, users_bf.dtype, items_bf.dtype) == "stream" and N > 4096 and stats is None
     flags = torch.empty(2, dtype=torch.int32, device=dev)
-    kk = min(k, k2)
     _chk(users_f32, "users_f32", torch.float32)
     _chk(items_f32, "items_f32", torch.float32)
 
-    def attempt(defer):
-        bv, bi, tau, _ = catalog_decode(users_bf, H, items_bf, tag_bits, row_bits, hist_ptr, hist_items, k2, stats=stats, n_items=N,
-                                        k_min=k, margin=2 * BF16_SCORE_ERR, defer_check=flags[0:1] if defer else None, target=target)
-        if tau is None:
-            # the GEMM scorer (its small-catalog form too) reports no threshold, which certifies nothing: +inf flags every row and
-            # all of them take the dense fp32 repair below (the other scorers' small-catalog forms report tau = -inf)
-            tau = torch.full((n_rows,), float("inf"), dtype=torch.float32, device=dev)
-        bv = bv.contiguous()
-        cnt = torch.empty(n_rows, dtype=torch.int32, device=dev)          # the margin set: a prefix of the sorted list
-        lib.call("mhr_topk_margin_count", bv.data_ptr(), n_rows, k2, kk, 2 * BF16_SCORE_ERR, cnt.data_ptr(), _stream())
-        rv = torch.empty(n_rows, k2, dtype=torch.float32, device=dev)
-        ri = torch.empty(n_rows, k2, dtype=torch.int32, device=dev)
+    def rescore(bi, cnt, rv, ri):
         lib.call("mhr_rescore_f32", users_f32.data_ptr(), items_f32.data_ptr(), D, N, bi.data_ptr(), n_rows, k2, cnt.data_ptr(),
                  rv.data_ptr(), ri.data_ptr(), _stream())
-        ov, oi, _, st = topk_select((rv, ri, cnt), k2, k)
-        # uncertified rows: the margin reaches below the emit threshold, or fills the candidate list (the (k2+1)-th bf16 score
-        # might be inside it too)
-        full = torch.empty(n_rows, dtype=torch.bool, device=dev)
-        lib.call("mhr_topk_uncertified", cnt.data_ptr(), bv.data_ptr(), k2, kk, tau.contiguous().data_ptr(), 1 if k2 < N - 1 else 0,
-                 2 * BF16_SCORE_ERR, n_rows, full.data_ptr(), flags[1:2].data_ptr(), _stream())
-        return ov, oi, cnt, full
+
+    def attempt(defer):
+        return _exact_attempt(users_bf, H, items_bf, N, tag_bits, row_bits, hist_ptr, hist_items, k, k2, flags, defer, stats, target,
+                              rescore)
 
     if defer and not deferred:
         raise ValueError("catalog_topk_exact(defer=True) needs the streaming scorer's deferred check (feature dim <= 256, N > 4096, no stats)")
@@ -1569,6 +1586,123 @@ def catalog_topk_exact(users_f32, H, items_bf, items_f32, tag_bits, row_bits, hi
     if defer:
         return ov, oi, finish
     return finish()
+
+
+MEAN_MAX_PATTERNS = 32     # distinct tag words of a catalog the average-mode decode takes: one bit of a row-bits word each
+
+
+def tag_patterns(tag_bits):
+    """The pattern table of catalog_topk_mean: (words [P] int32: the distinct tag words of the catalog, pattern_bits [N] int32 =
+    1 << (position of tag_bits[n] in words)).  tag_bits None (no tag table: every item carries bit 31): ([bit 31], None).
+    Plain torch on whatever device tag_bits lives on; once per (item table, tags)."""
+    if tag_bits is None:
+        return torch.tensor([-(1 << 31)], dtype=torch.int32), None
+    words, pid = torch.unique(tag_bits, return_inverse=True)
+    if words.numel() > MEAN_MAX_PATTERNS:
+        raise ValueError(f"split_mode=average: the catalog holds {words.numel()} distinct tag words, the fused decode takes at most "
+                         f"{MEAN_MAX_PATTERNS}; rank such a catalog through predict() and the collector's dense average branch")
+    bits = torch.ones_like(pid, dtype=torch.int64) << pid.long()
+    return words.to(torch.int32), torch.where(bits >= (1 << 31), bits - (1 << 32), bits).to(torch.int32).contiguous()
+
+
+def mean_rows_dense_topk(heads_f32, items_f32, n_items, tag_bits, row_bits, hist_ptr, hist_items, users, k):
+    """Exact top-k (value desc, index asc) of the MEAN over finite heads for the users `users` (int32 [F]) with every item's mean
+    kept: `mhr_catalog_mean_rows_dense` (pad / history / tag / row-bit masks as in the reference, items masked in every head at
+    0.0 - collector.py:227-230) + the exact select over the whole row.  heads_f32 [B, H, D], items_f32 [N, D] fp32 normalised.
+    -> (values [F, k] f32, indices [F, k] i64)."""
+    B, H, D = heads_f32.shape
+    N, dev = int(n_items), heads_f32.device
+    users = users.to(torch.int32).contiguous()
+    F_ = users.numel()
+    ov = torch.empty(F_, k, dtype=torch.float32, device=dev)
+    oi = torch.empty(F_, k, dtype=torch.int64, device=dev)
+    for r0 in range(0, F_, DENSE_ROWS_CHUNK):                              # one scratch row per USER: the budget of dense_rows_topk
+        r1 = min(F_, r0 + DENSE_ROWS_CHUNK)
+        val = torch.empty(r1 - r0, N, dtype=torch.float32, device=dev)
+        idx = torch.empty(r1 - r0, N, dtype=torch.int32, device=dev)
+        cnt = torch.empty(r1 - r0, dtype=torch.int32, device=dev)
+        _timed_call("mhr_catalog_mean_rows_dense", heads_f32.data_ptr(), items_f32.data_ptr(), D, N, users[r0:r1].data_ptr(), r1 - r0, H,
+                    _ptr(tag_bits), row_bits.data_ptr(), _ptr(hist_ptr), _ptr(hist_items), val.data_ptr(), idx.data_ptr(),
+                    cnt.data_ptr(), _stream())
+        fv, fi, _, _ = topk_select((val, idx, cnt), N, k)
+        ov[r0:r1], oi[r0:r1] = fv, fi
+    return ov, oi
+
+
+def catalog_topk_mean(heads_f32, items_bf, items_f32, tag_bits, row_bits, hist_ptr, hist_items, k, patterns=None, n_items=None,
+                      stats=None, target=None):
+    """split_mode = average without a [B, H, N] tensor: per-user top-k of the mean over FINITE heads of the fp32 scores (reference
+    collector.py:227-230 on the masks of hstu.py:982-1015 and trainer.py:724-726), ranked (fp32 value desc, index asc).
+    Head h is finite for item n iff n is not the pad id, not in the history and row_bits[b,h] & tag_bits[n] != 0: the finite set
+    depends on n only through its tag word w, and the dot product is linear, so mean(b, n) = <q[b,w], i[n]> with q[b,w] the mean of
+    the heads live for w.  The decode is therefore catalog_topk_exact's, single-headed, with P = (distinct tag words) query rows per
+    user (`mhr_head_mean_queries`), each restricted to the items of its word by a one-hot pattern word per item in place of
+    tag_bits and 1 << p per query row in place of row_bits; the candidates are re-scored with the reference's own arithmetic
+    (`mhr_rescore_mean_f32`: H fp32 dots, finite ones summed, / count) and the P disjoint lists of a user merged.
+    Two reference quirks: count + 1e-8 == count in fp32 (count >= 1), and an item masked in EVERY head scores 0 / 1e-8 = 0, not
+    -inf, so it outranks negative means.  The merged list of a user is therefore trusted only when its k-th value is > 0; users
+    where it is not (small catalogs), and users with an uncertified row, are re-ranked from every item's mean
+    (`mhr_catalog_mean_rows_dense` + the exact select), zeros included.  Ties of exactly equal means ACROSS two patterns come out
+    in pattern order (the merge's rule), within a pattern and on the dense path by ascending index.
+    heads_f32 [B, H, D] fp32 normalised, items_bf [>= N, D] bf16 / items_f32 [N, D] fp32 normalised, tag_bits [N] int32 or None,
+    row_bits [B*H] int32, history CSR over the B users; patterns: tag_patterns(tag_bits) (computed here when None).
+    Sizes: P <= 32 (tag_patterns), P * k <= 8192 (the merge), H * D <= 16000 (the dense repair keeps a user's head rows in LDS).
+    ONE host read per call on the streaming path (the bf16 pass's flag, the uncertified flag and the per-user flags together);
+    a second one only when the bf16 pass's thresholds came up short and it is repeated.
+    stats: patterns, margin_mean, uncertified_rows, dense_users (the list of re-ranked users).  -> (values [B, k] f32, indices [B, k] i64)."""
+    _chk(heads_f32, "heads_f32", torch.float32)
+    _chk(items_f32, "items_f32", torch.float32)
+    B, H, D = heads_f32.shape
+    N = items_f32.shape[0] if n_items is None else int(n_items)
+    dev = heads_f32.device
+    words, pattern_bits = tag_patterns(tag_bits) if patterns is None else patterns
+    words = words.to(dev).contiguous()
+    P = words.numel()
+    if (pattern_bits is None) != (tag_bits is None) or (pattern_bits is None and P != 1):
+        raise ValueError("catalog_topk_mean: patterns must come from tag_patterns(tag_bits)")
+    q = torch.empty(B * P, D, dtype=torch.float32, device=dev)
+    q_bits = torch.empty(B * P, dtype=torch.int32, device=dev)
+    _timed_call("mhr_head_mean_queries", heads_f32.data_ptr(), row_bits.data_ptr(), words.data_ptr(), B, H, P, D,
+                0 if pattern_bits is None else 1, q.data_ptr(), q_bits.data_ptr(), _stream())
+    # |q| <= 1 (a mean of unit vectors), so the bf16 scorer's error bound 2^-8 holds for <q_bf16, i_bf16> as it does for a head row;
+    # the fp32 difference between <q, i> and the mean of the H dots (about H * 2^-24) fits in the bound's slack (2^-8 is reached
+    # only when every component's rounding error has the sign of the other operand's component)
+    q_bf = q.to(torch.bfloat16)
+    k2 = _margin_slots(N, k, D)
+    deferred = decode_path(D, q_bf.dtype, items_bf.dtype) == "stream" and N > 4096 and stats is None
+    flags = torch.empty(2, dtype=torch.int32, device=dev)
+    n_rows = B * P
+
+    def rescore(bi, cnt, rv, ri):
+        _timed_call("mhr_rescore_mean_f32", heads_f32.data_ptr(), items_f32.data_ptr(), D, N, H, P, _ptr(tag_bits), row_bits.data_ptr(),
+                    bi.data_ptr(), n_rows, k2, cnt.data_ptr(), rv.data_ptr(), ri.data_ptr(), _stream())
+
+    def attempt(defer):
+        ov, oi, cnt, full = _exact_attempt(q_bf, P, items_bf, N, pattern_bits, q_bits, hist_ptr, hist_items, k, k2, flags, defer, stats,
+                                           target, rescore)
+        if P > 1:                      # the P lists of a user hold disjoint item sets: the merge only merges
+            mi, mv, _, uniq = multihead_merge_dedup(ov.view(B, P, k), oi.view(B, P, k), B, P, k)
+            short = uniq < k           # (-inf completions of short lists may repeat an id; such a list ends <= 0 anyway)
+        else:
+            mv, mi, short = ov, oi, torch.zeros(B, dtype=torch.bool, device=dev)
+        # a user is re-ranked densely when a row of his is uncertified or his k-th mean is not > 0: then items masked in every
+        # head (mean 0 in the reference) belong in his list
+        dense = full.view(B, P).any(dim=1) | short | ~(mv[:, k - 1] > 0)
+        return mv, mi, cnt, full, dense
+
+    mv, mi, cnt, full, dense = attempt(deferred)
+    got = torch.cat([flags, dense.to(torch.int32)]).tolist()                  # the one host sync
+    if deferred and got[0]:
+        mv, mi, cnt, full, dense = attempt(False)
+        got = torch.cat([flags, dense.to(torch.int32)]).tolist()
+    users_f = [b for b in range(B) if got[2 + b]]
+    if stats is not None:
+        stats.update(patterns=P, margin_mean=float(cnt.float().mean()), uncertified_rows=int(full.sum()), dense_users=users_f)
+    if users_f:
+        users_t = torch.tensor(users_f, dtype=torch.int32, device=dev)
+        fv, fi = mean_rows_dense_topk(heads_f32, items_f32, N, tag_bits, row_bits, hist_ptr, hist_items, users_t, k)
+        mv[users_t.long()], mi[users_t.long()] = fv, fi
+    return mv, mi
 
 
 def multihead_merge_dedup(vals, idx, B, H, k):
