@@ -139,6 +139,40 @@ int mhr_adam_rows_lazy(float* w, float* m, float* v, int64_t n_rows, int dim, co
                        int hist_len, int step, float grad_scale, float beta1, float beta2, float eps, int mode,
                        const int64_t* step_dev, void* stream);
 
+/* Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, norm_type 2, error_if_nonfinite False; the reference's
+ * `clip_grad_norm`, trainer.py:99, and the `grad_norm` it logs, trainer.py:532, 552-553), without a host read.
+ *   mhr_grad_sqnorm_partials(n, dim): HOST size query, no launch - the number of fp64 partials a launch over n rows of
+ *     `dim` elements writes (the flat form is dim = 1).  Monotone in n, 1 at n = 0 (one zero is written), -1 on bad sizes.
+ *   mhr_grad_sqnorm_flat: partials[off + k] = sum of g[i]^2 over the k-th fixed range of g [n] f32 (16-byte aligned).
+ *   mhr_grad_sqnorm_rows: the same over the rows [n_ids, dim] f32 of a sparse row gradient (mhr_sparse_rows_segment_sum's
+ *     out_rows; dim % 4 == 0): row i counts where sorted_ids[i] starts a segment and lies in [0, n_rows) - exactly the rows the
+ *     Adam kernels apply; the other rows are not read.
+ *   Both accumulate in fp64, every workgroup over a contiguous range that depends on the sizes only, and write one partial
+ *   per workgroup: no atomics, so the result is a pure function of the input bits.
+ *   mhr_grad_clip_coef: one workgroup folds partials[0, n_partials) in a fixed order and writes out2 (device float[2]):
+ *     out2[0] = total_norm = sqrt(sum) * pre_scale   (pre_scale = 1 / world size: the norm of the AVERAGED gradient),
+ *     out2[1] = pre_scale * min(1, max_norm / (total_norm + 1e-6)) - the whole gradient scale of the step.
+ *     A non-finite norm propagates as torch's formula propagates it.  max_norm > 0, pre_scale > 0.
+ *   mhr_adam_*_scaled: the entries above plus scale_dev (device float[2], the record of mhr_grad_clip_coef): the kernels multiply
+ *     the gradient by scale_dev[1] instead of `grad_scale`; nothing else differs (mhr_adam_rows_lazy_scaled: mode 1 only). */
+int64_t mhr_grad_sqnorm_partials(int64_t n, int dim);
+int mhr_grad_sqnorm_flat(const float* g, int64_t n, double* partials, int64_t partials_off, void* stream);
+int mhr_grad_sqnorm_rows(const float* rows, const int64_t* sorted_ids, int64_t n_ids, int dim, int64_t n_rows,
+                         double* partials, int64_t partials_off, void* stream);
+int mhr_grad_clip_coef(const double* partials, int64_t n_partials, float pre_scale, float max_norm, float* out2,
+                       void* stream);
+int mhr_adam_flat_scaled(float* w, const float* g, float* m, float* v, int64_t n, float grad_scale,
+                         float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* w_bf16,
+                         const float* hist, int hist_len, const int64_t* step_dev, const float* scale_dev, void* stream);
+int mhr_adam_rows_scaled(float* w, float* m, float* v, int64_t n_rows, int dim,
+                         const float* grad_rows, int32_t* row_slot, float grad_scale,
+                         float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                         const float* scale_dev, void* stream);
+int mhr_adam_rows_lazy_scaled(float* w, float* m, float* v, int64_t n_rows, int dim, const int64_t* ids, int64_t n_ids,
+                              const float* grad_rows, int32_t* row_slot, int32_t* last_step, const float* hist,
+                              int hist_len, int step, float grad_scale, float beta1, float beta2, float eps, int mode,
+                              const int64_t* step_dev, const float* scale_dev, void* stream);
+
 /* out[c] += sum_r x[r, c]: x bf16 [rows, cols] (cols % 8 == 0), out fp32 [cols].  The reduction of split-K weight-gradient
  * partials and of bias gradients straight into the flat gradient buffer (autograd's accumulate semantics: the caller
  * zeroes the buffer once per step).  Many-row inputs are reduced by several workgroups meeting through float atomics. */

@@ -328,7 +328,7 @@ class Trainer(object):
         # when they are next read (bitwise the dense result; `lazy_table_adam: False` restores the dense pass per step)
         lazy = self.config.get('lazy_table_adam', True) and not getattr(model, "dense_embedding_grad", False)
         self.optimizer = FusedAdamW(model, lr=self.optim_args['learning_rate'], weight_decay=self.optim_args['weight_decay'],
-                                    lazy_table=bool(lazy))
+                                    lazy_table=bool(lazy), clip_grad_norm=self.config.get('clip_grad_norm'))
         self._micro_step = 0
         if self.accumulate_grad == 1 and hasattr(self.optimizer, "enable_partial_arena"):
             self.optimizer.enable_partial_arena(True)     # one backward per step: all split-K partials summed by one launch
@@ -464,7 +464,10 @@ class Trainer(object):
                 self._check_nan(out["loss"])
                 if self.rank == 0:
                     extra = {k: (float(v) if torch.is_tensor(v) else v) for k, v in out.items() if k != "loss"}
-                    self.logger.info(f"step {self.train_step} loss {loss:.4f} lr {self.optimizer.param_groups[0]['lr']:.3e} "
+                    # the pre-clip gradient norm of the step just read (reference trainer.py:532, 552-553): the device is idle
+                    # after the loss read, so this word costs no further wait
+                    norm = "" if self.optimizer.grad_norm is None else f"grad_norm {float(self.optimizer.grad_norm):.4f} "
+                    self.logger.info(f"step {self.train_step} loss {loss:.4f} {norm}lr {self.optimizer.param_groups[0]['lr']:.3e} "
                                      f"{(time.time() - t0) / self.train_step:.3f}s/step {extra}")
             if valid_data is not None and self.eval_interval and self.train_step % self.eval_interval == 0:
                 result = self.evaluate(valid_data, load_best_model=False)

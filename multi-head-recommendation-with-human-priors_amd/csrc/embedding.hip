@@ -611,7 +611,9 @@ __device__ __forceinline__ void adam_update4(f32x4& w, f32x4& m, f32x4& v, f32x4
 
 __global__ __launch_bounds__(256) void adam_rows_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
                                                         int64_t n_rows, int dim, const float* __restrict__ grad_rows,
-                                                        int32_t* __restrict__ row_slot, AdamConst a) {
+                                                        int32_t* __restrict__ row_slot, AdamConst a,
+                                                        const float* __restrict__ scale_dev) {
+  if (scale_dev) a.grad_scale = scale_dev[1];   // clipped step: the whole gradient scale from the device (mhr_grad_clip_coef)
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
@@ -633,17 +635,32 @@ __global__ __launch_bounds__(256) void adam_rows_kernel(float* __restrict__ w, f
   }
 }
 
-extern "C" int mhr_adam_rows(float* w, float* m, float* v, int64_t n_rows, int dim, const float* grad_rows,
-                             int32_t* row_slot, float grad_scale, float lr, float beta1, float beta2, float eps,
-                             float weight_decay, int step, void* stream) {
+static int adam_rows_launch(float* w, float* m, float* v, int64_t n_rows, int dim, const float* grad_rows,
+                            int32_t* row_slot, float grad_scale, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, const float* scale_dev, void* stream) {
   MHR_REQUIRE(w && m && v && grad_rows, "adam_rows: null pointer");
   MHR_REQUIRE(dim > 0 && dim % 4 == 0 && n_rows > 0 && step >= 1, "adam_rows: bad sizes (dim=%d step=%d)", dim, step);
   AdamConst a = make_adam(lr, beta1, beta2, eps, weight_decay, step, grad_scale);
   int grid = mhr_grid_for(n_rows, 4 * 4);
   hipLaunchKernelGGL(adam_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, m, v, n_rows, dim, grad_rows,
-                     row_slot, a);
+                     row_slot, a, scale_dev);
   MHR_CHECK_LAUNCH("adam_rows");
   return MHR_OK;
+}
+
+extern "C" int mhr_adam_rows(float* w, float* m, float* v, int64_t n_rows, int dim, const float* grad_rows,
+                             int32_t* row_slot, float grad_scale, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int step, void* stream) {
+  return adam_rows_launch(w, m, v, n_rows, dim, grad_rows, row_slot, grad_scale, lr, beta1, beta2, eps, weight_decay, step,
+                          nullptr, stream);
+}
+
+extern "C" int mhr_adam_rows_scaled(float* w, float* m, float* v, int64_t n_rows, int dim, const float* grad_rows,
+                                    int32_t* row_slot, float grad_scale, float lr, float beta1, float beta2, float eps,
+                                    float weight_decay, int step, const float* scale_dev, void* stream) {
+  MHR_REQUIRE(scale_dev, "adam_rows_scaled: null scale_dev");
+  return adam_rows_launch(w, m, v, n_rows, dim, grad_rows, row_slot, grad_scale, lr, beta1, beta2, eps, weight_decay, step,
+                          scale_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -674,8 +691,10 @@ __global__ __launch_bounds__(256) void adam_rows_lazy_kernel(float* __restrict__
                                                              int64_t n_ids, const float* __restrict__ grad_rows,
                                                              int32_t* __restrict__ row_slot, int32_t* __restrict__ last_step,
                                                              const float* __restrict__ hist, AdamLazy a,
-                                                             const int64_t* __restrict__ step_dev) {
+                                                             const int64_t* __restrict__ step_dev,
+                                                             const float* __restrict__ scale_dev) {
   if (step_dev) a.step = (int)step_dev[0];      // hipGraph-replayed step: the step number lives in device memory
+  if (scale_dev) a.grad_scale = scale_dev[1];   // clipped step (mode 1 only: the other modes apply no gradient)
   const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x >> 6);
@@ -727,10 +746,10 @@ extern "C" int mhr_adam_consts(float lr, float beta1, float beta2, float eps, fl
   return MHR_OK;
 }
 
-extern "C" int mhr_adam_rows_lazy(float* w, float* m, float* v, int64_t n_rows, int dim, const int64_t* ids, int64_t n_ids,
-                                  const float* grad_rows, int32_t* row_slot, int32_t* last_step, const float* hist,
-                                  int hist_len, int step, float grad_scale, float beta1, float beta2, float eps, int mode,
-                                  const int64_t* step_dev, void* stream) {
+static int adam_rows_lazy_launch(float* w, float* m, float* v, int64_t n_rows, int dim, const int64_t* ids, int64_t n_ids,
+                                 const float* grad_rows, int32_t* row_slot, int32_t* last_step, const float* hist,
+                                 int hist_len, int step, float grad_scale, float beta1, float beta2, float eps, int mode,
+                                 const int64_t* step_dev, const float* scale_dev, void* stream) {
   MHR_REQUIRE(w && m && v && last_step && hist, "adam_rows_lazy: null pointer");
   MHR_REQUIRE(mode >= 0 && mode <= 2 && (mode == 2 || ids) && (mode != 1 || grad_rows), "adam_rows_lazy: bad mode / inputs");
   MHR_REQUIRE(dim > 0 && dim % 4 == 0 && n_rows > 0 && hist_len > 0 && step >= 0, "adam_rows_lazy: bad sizes");
@@ -741,16 +760,35 @@ extern "C" int mhr_adam_rows_lazy(float* w, float* m, float* v, int64_t n_rows, 
   a.grad_scale = grad_scale; a.hist_len = hist_len; a.step = step; a.mode = mode;
   int grid = mhr_grid_for(n_work, 4 * 4);
   hipLaunchKernelGGL(adam_rows_lazy_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, m, v, n_rows, dim, ids, n_ids,
-                     grad_rows, row_slot, last_step, hist, a, step_dev);
+                     grad_rows, row_slot, last_step, hist, a, step_dev, scale_dev);
   MHR_CHECK_LAUNCH("adam_rows_lazy");
   return MHR_OK;
+}
+
+extern "C" int mhr_adam_rows_lazy(float* w, float* m, float* v, int64_t n_rows, int dim, const int64_t* ids, int64_t n_ids,
+                                  const float* grad_rows, int32_t* row_slot, int32_t* last_step, const float* hist,
+                                  int hist_len, int step, float grad_scale, float beta1, float beta2, float eps, int mode,
+                                  const int64_t* step_dev, void* stream) {
+  return adam_rows_lazy_launch(w, m, v, n_rows, dim, ids, n_ids, grad_rows, row_slot, last_step, hist, hist_len, step,
+                               grad_scale, beta1, beta2, eps, mode, step_dev, nullptr, stream);
+}
+
+extern "C" int mhr_adam_rows_lazy_scaled(float* w, float* m, float* v, int64_t n_rows, int dim, const int64_t* ids,
+                                         int64_t n_ids, const float* grad_rows, int32_t* row_slot, int32_t* last_step,
+                                         const float* hist, int hist_len, int step, float grad_scale, float beta1, float beta2,
+                                         float eps, int mode, const int64_t* step_dev, const float* scale_dev, void* stream) {
+  MHR_REQUIRE(scale_dev && mode == 1, "adam_rows_lazy_scaled: needs scale_dev and mode 1 (the other modes apply no gradient)");
+  return adam_rows_lazy_launch(w, m, v, n_rows, dim, ids, n_ids, grad_rows, row_slot, last_step, hist, hist_len, step,
+                               grad_scale, beta1, beta2, eps, mode, step_dev, scale_dev, stream);
 }
 
 __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ w, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                         AdamConst a, bf16_t* __restrict__ w16,
                                                         const float* __restrict__ hist, int hist_len,
-                                                        const int64_t* __restrict__ step_dev) {
+                                                        const int64_t* __restrict__ step_dev,
+                                                        const float* __restrict__ scale_dev) {
+  if (scale_dev) a.grad_scale = scale_dev[1];   // clipped step: the whole gradient scale from the device (mhr_grad_clip_coef)
   if (step_dev) {       // hipGraph-replayed step: this step's constants from the device-side history (mhr_adam_consts rows)
     const float* h = hist + (step_dev[0] % hist_len) * 4;
     a.decay_mul = h[0]; a.step_size = h[1]; a.inv_sqrt_bc2 = h[2];
@@ -779,9 +817,9 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ w, c
   }
 }
 
-extern "C" int mhr_adam_flat(float* w, const float* g, float* m, float* v, int64_t n, float grad_scale, float lr,
-                             float beta1, float beta2, float eps, float weight_decay, int step, void* w_bf16,
-                             const float* hist, int hist_len, const int64_t* step_dev, void* stream) {
+static int adam_flat_launch(float* w, const float* g, float* m, float* v, int64_t n, float grad_scale, float lr,
+                            float beta1, float beta2, float eps, float weight_decay, int step, void* w_bf16,
+                            const float* hist, int hist_len, const int64_t* step_dev, const float* scale_dev, void* stream) {
   MHR_REQUIRE(w && g && m && v, "adam_flat: null pointer");
   MHR_REQUIRE(!step_dev || (hist && hist_len > 0), "adam_flat: step_dev needs the constants' history");
   MHR_REQUIRE(!w_bf16 || (uintptr_t)w_bf16 % 8 == 0, "adam_flat: the bf16 shadow must be 8-byte aligned");
@@ -792,7 +830,23 @@ extern "C" int mhr_adam_flat(float* w, const float* g, float* m, float* v, int64
   AdamConst a = make_adam(lr, beta1, beta2, eps, weight_decay, step, grad_scale);
   int grid = mhr_grid_for(n / 4 + 1, 256, 2048);
   hipLaunchKernelGGL(adam_flat_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, g, m, v, n, a, (bf16_t*)w_bf16,
-                     hist, hist_len, step_dev);
+                     hist, hist_len, step_dev, scale_dev);
   MHR_CHECK_LAUNCH("adam_flat");
   return MHR_OK;
+}
+
+extern "C" int mhr_adam_flat(float* w, const float* g, float* m, float* v, int64_t n, float grad_scale, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, int step, void* w_bf16,
+                             const float* hist, int hist_len, const int64_t* step_dev, void* stream) {
+  return adam_flat_launch(w, g, m, v, n, grad_scale, lr, beta1, beta2, eps, weight_decay, step, w_bf16, hist, hist_len,
+                          step_dev, nullptr, stream);
+}
+
+extern "C" int mhr_adam_flat_scaled(float* w, const float* g, float* m, float* v, int64_t n, float grad_scale, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, int step, void* w_bf16,
+                                    const float* hist, int hist_len, const int64_t* step_dev, const float* scale_dev,
+                                    void* stream) {
+  MHR_REQUIRE(scale_dev, "adam_flat_scaled: null scale_dev");
+  return adam_flat_launch(w, g, m, v, n, grad_scale, lr, beta1, beta2, eps, weight_decay, step, w_bf16, hist, hist_len,
+                          step_dev, scale_dev, stream);
 }

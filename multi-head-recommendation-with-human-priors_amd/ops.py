@@ -182,17 +182,76 @@ def window_rows_add_packed(rows, window, L, d_x, row_of, out=None):
     return out
 
 
-def adam_rows(w, m, v, grad_rows, row_slot, step, lr, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+def adam_rows(w, m, v, grad_rows, row_slot, step, lr, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+              scale_dev=None):
+    """scale_dev (device float[2], `grad_clip_coef`'s record): the gradient scale is scale_dev[1] instead of grad_scale."""
+    if scale_dev is not None:
+        _timed_call("mhr_adam_rows_scaled", w.data_ptr(), m.data_ptr(), v.data_ptr(), w.shape[0], w.shape[1],
+                    grad_rows.data_ptr(), _ptr(row_slot), grad_scale, lr, betas[0], betas[1], eps, weight_decay, step,
+                    _chk(scale_dev, "scale_dev", torch.float32).data_ptr(), _stream())
+        return
     _timed_call("mhr_adam_rows", w.data_ptr(), m.data_ptr(), v.data_ptr(), w.shape[0], w.shape[1], grad_rows.data_ptr(),
              _ptr(row_slot), grad_scale, lr, betas[0], betas[1], eps, weight_decay, step, _stream())
 
 
 def adam_flat(w, g, m, v, step, lr, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, w_bf16=None,
-              hist=None, step_dev=None, hist_len=64):
-    """hist [hist_len, 4] f32 + step_dev int64[1] (device): the step's constants come from device memory (hipGraph replay)."""
+              hist=None, step_dev=None, hist_len=64, scale_dev=None):
+    """hist [hist_len, 4] f32 + step_dev int64[1] (device): the step's constants come from device memory (hipGraph replay).
+    scale_dev (device float[2], `grad_clip_coef`'s record): the gradient scale is scale_dev[1] instead of grad_scale."""
+    if scale_dev is not None:
+        _timed_call("mhr_adam_flat_scaled", w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), grad_scale, lr,
+                    betas[0], betas[1], eps, weight_decay, step, _ptr(w_bf16), _ptr(hist), 0 if hist is None else hist_len,
+                    _ptr(step_dev), _chk(scale_dev, "scale_dev", torch.float32).data_ptr(), _stream())
+        return
     lib.call("mhr_adam_flat", w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), grad_scale, lr,
              betas[0], betas[1], eps, weight_decay, step, _ptr(w_bf16), _ptr(hist), 0 if hist is None else hist_len,
              _ptr(step_dev), _stream())
+
+
+def grad_sqnorm_partials(n, dim=1):
+    """How many fp64 partials `grad_sqnorm_flat` over n elements (dim = 1) / `grad_sqnorm_rows` over n rows of `dim` writes
+    (a host size query; 1 at n = 0)."""
+    p = lib.load().mhr_grad_sqnorm_partials(int(n), int(dim))
+    if p < 0:
+        raise ValueError(f"grad_sqnorm_partials: bad sizes (n={n}, dim={dim})")
+    return int(p)
+
+
+def grad_sqnorm_flat(g, partials, off=0):
+    """partials[off + k] (fp64) = the sum of squares of the k-th fixed range of the flat fp32 tensor g; returns the count."""
+    _chk(g, "g", torch.float32)
+    _chk(partials, "partials", torch.float64)
+    n = g.numel()
+    p = grad_sqnorm_partials(n)
+    assert off >= 0 and off + p <= partials.numel(), "grad_sqnorm_flat: the partials buffer is too small"
+    _timed_call("mhr_grad_sqnorm_flat", g.data_ptr(), n, partials.data_ptr(), int(off), _stream())
+    return p
+
+
+def grad_sqnorm_rows(rows, sorted_ids, n_rows, partials, off=0):
+    """The same over the segment-head rows of a sparse row gradient (rows [n_ids, D] fp32, sorted_ids [n_ids] int64) whose id
+    lies in [0, n_rows): the rows the table Adam applies.  Returns the count of partials written."""
+    _chk(rows, "rows", torch.float32)
+    _chk(sorted_ids, "sorted_ids", torch.int64)
+    _chk(partials, "partials", torch.float64)
+    n_ids, D = sorted_ids.numel(), rows.shape[-1]
+    assert rows.numel() == n_ids * D
+    p = grad_sqnorm_partials(n_ids, D)
+    assert off >= 0 and off + p <= partials.numel(), "grad_sqnorm_rows: the partials buffer is too small"
+    _timed_call("mhr_grad_sqnorm_rows", rows.data_ptr(), sorted_ids.data_ptr(), n_ids, D, int(n_rows), partials.data_ptr(),
+                int(off), _stream())
+    return p
+
+
+def grad_clip_coef(partials, n_partials, pre_scale, max_norm, out2):
+    """out2 (device float[2]) = {total_norm, pre_scale * min(1, max_norm / (total_norm + 1e-6))} with
+    total_norm = sqrt(partials[:n_partials].sum()) * pre_scale - torch's clip_grad_norm_ coefficient, left on the device."""
+    _chk(partials, "partials", torch.float64)
+    _chk(out2, "out2", torch.float32)
+    assert 0 <= n_partials <= partials.numel() and out2.numel() >= 2
+    _timed_call("mhr_grad_clip_coef", partials.data_ptr(), int(n_partials), float(pre_scale), float(max_norm),
+                out2.data_ptr(), _stream())
+    return out2
 
 
 def heads_residual_fwd(x, z, B, L, H):

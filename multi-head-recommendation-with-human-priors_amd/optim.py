@@ -54,8 +54,13 @@ LAZY_HIST = 64        # steps a table row may lag behind before everything is fl
 
 
 class FusedAdamW:
-    def __init__(self, model, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, lazy_table=False):
-        """lazy_table: update only the rows a step touches and replay the gradient-free steps of a row when it is next read
+    def __init__(self, model, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, lazy_table=False, clip_grad_norm=None):
+        """clip_grad_norm (None or <= 0: off, exactly the unclipped step): clip the gradient by its global L2 norm over every
+        trainable parameter (torch.nn.utils.clip_grad_norm_; the reference's `clip_grad_norm`, trainer.py:99).  The norm is
+        reduced on the device and the Adam kernels read the resulting scale from device memory (`_clip_state`): no host read, so
+        a clipped step replays from a hipGraph like any other.  `grad_norm` (device fp32 scalar) holds the last step's pre-clip
+        norm (the reference's log value, trainer.py:532, 552-553).
+        lazy_table: update only the rows a step touches and replay the gradient-free steps of a row when it is next read
         (`catch_up`, called by the model's training forward) or flushed (`flush_table`: evaluation, checkpoints, state_dict,
         every LAZY_HIST steps).  Bitwise the same weights as the dense update; the model must read the table through those
         hooks (HSTU does) - leave it off for code that reads `item_embedding.weight` directly while training."""
@@ -133,6 +138,18 @@ class FusedAdamW:
             self.last_step = torch.zeros(self.table.shape[0], dtype=torch.int32, device=dev)
             model._table_optimizer = self                                # the model's forward / eval hooks find us here
             self._lagging = False                                        # rows behind step_count exist (host-side flag)
+        self.clip_grad_norm = float(clip_grad_norm) if clip_grad_norm is not None and float(clip_grad_norm) > 0 else None
+        self.grad_norm = None
+        if self.clip_grad_norm is not None:
+            # fp64 partials of the squared norm (flat gradient first, then the table's rows) and the record the coefficient
+            # launch leaves for the Adam kernels: {total_norm, 1/W * coef}.  Allocated here, never under capture; sized for a
+            # row set as long as the table (or the dense table gradient) and regrown by a host-issued step that needs more.
+            self._clip_p_flat = ops.grad_sqnorm_partials(total)
+            n_tab = 0 if self.table is None else max(ops.grad_sqnorm_partials(self.table.shape[0], self.table.shape[1]),
+                                                     ops.grad_sqnorm_partials(self.table.numel()))
+            self._clip_partials = torch.zeros(self._clip_p_flat + n_tab, dtype=torch.float64, device=dev)
+            self._clip_state = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.grad_norm = self._clip_state[0]
 
     # ---- split-K partials of ALL weight gradients in one arena, reduced by ONE launch at the step -------------------------
     def enable_partial_arena(self, on=True):
@@ -297,7 +314,8 @@ class FusedAdamW:
 
     def graph_capable(self):
         """A step can be replayed from a hipGraph when every per-step scalar can come from device memory: the flat Adam and
-        the lazy table Adam can; the dense table pass (`mhr_adam_rows`) takes its constants as arguments."""
+        the lazy table Adam can; the dense table pass (`mhr_adam_rows`) takes its constants as arguments.  (Clipping changes
+        nothing here: `clip_grad_norm` is a constant of the capture, the norm and the scale live in device memory.)"""
         return self.table is None or self.lazy
 
     def begin_replayed_step(self, lr, seed_counter=0):
@@ -314,6 +332,8 @@ class FusedAdamW:
             self.flush_table()
 
     def step(self):
+        if self.clip_grad_norm is not None:
+            return self._step_clipped()
         self.step_count += 1
         lr = self.param_groups[0]["lr"]
         W = D.world_size()
@@ -355,6 +375,73 @@ class FusedAdamW:
             ops.adam_rows(self.table, self.t_m, self.t_v, g, None, self.step_count, lr, 1.0, self.betas, self.eps,
                           self.weight_decay)
 
+    # ---- the step with gradient clipping --------------------------------------------------------
+    def _clip_room(self, need):
+        """Room for `need` partials behind the flat gradient's (grow-only; a captured step cannot allocate: the host-issued
+        warm-up steps of the same batch signature have sized the buffer before the capture)."""
+        if self._clip_p_flat + need > self._clip_partials.numel():
+            if self.in_graph:
+                raise RuntimeError("clip_grad_norm: the squared-norm partials buffer is too small for this captured step")
+            self.__dict__.setdefault("_clip_retired", []).append(self._clip_partials)    # captured graphs bake its address
+            self._clip_partials = torch.zeros(self._clip_p_flat + 2 * need, dtype=torch.float64, device=self.flat_g.device)
+
+    def _step_clipped(self):
+        """step() with `clip_grad_norm`: the same launches, but every gradient is complete (deferred reductions folded,
+        data-parallel sums done, sparse rows segment-summed) before anything is applied, because the norm runs over all of it:
+        the flat Adam no longer runs underneath the row all-gather.  Then: squared-norm partials of the flat gradient and of the
+        table's gradient, ONE coefficient launch, and the Adam kernels with the device-side scale."""
+        self.step_count += 1
+        lr = self.param_groups[0]["lr"]
+        W = D.world_size()
+        self._reduce_arena()
+        dense_work = D.allreduce_sum_begin(self.flat_g)
+        if self.table is not None and hasattr(self.model, "begin_sparse_exchange"):
+            self.model.begin_sparse_exchange()
+        if dense_work is not None:
+            dense_work.wait()
+        sg = g_dense = None
+        if self.table is not None:
+            sg = self.model.finish_sparse_grad() if hasattr(self.model, "finish_sparse_grad") else self.model.sparse_grad
+            if sg is None and self.table.grad is not None:               # dense_embedding_grad mode
+                g_dense = self.table.grad
+                if self.lazy:                  # a dense step in between lazy ones: everything up to date first, and after it
+                    self.step_count -= 1
+                    self.flush_table()
+                    self.step_count += 1
+                    self.last_step.fill_(self.step_count)
+                table_work = D.allreduce_sum_begin(g_dense)              # the SUM: 1/W comes with the device-side scale
+                if table_work is not None:
+                    table_work.wait()
+        n_p = ops.grad_sqnorm_flat(self.flat_g, self._clip_partials, 0)
+        if sg is not None:
+            self._clip_room(ops.grad_sqnorm_partials(sg.sorted_ids.numel(), sg.rows.shape[-1]))
+            n_p += ops.grad_sqnorm_rows(sg.rows, sg.sorted_ids, self.table.shape[0], self._clip_partials, n_p)
+        elif g_dense is not None:
+            n_p += ops.grad_sqnorm_flat(g_dense.view(-1), self._clip_partials, n_p)
+        scale = ops.grad_clip_coef(self._clip_partials, n_p, 1.0 / W, self.clip_grad_norm, self._clip_state)
+        sd = self.step_dev if self.in_graph else None
+        ops.adam_flat(self.flat_w, self.flat_g, self.flat_m, self.flat_v, self.step_count, lr, 1.0 / W, self.betas, self.eps,
+                      self.weight_decay, w_bf16=self.flat_w16, hist=self.hist if sd is not None else None, step_dev=sd,
+                      scale_dev=scale)
+        for p in self.dense:
+            if hasattr(p, "_mhr_bf16"):
+                p._mhr_ver = p._version
+        if self.table is None:
+            return
+        if self.lazy and not self.in_graph:
+            self._push_consts(self.step_count, lr)
+        if sg is not None and self.lazy:
+            self._lazy_call(1, sg.sorted_ids, sg.rows, sg.row_slot, 1.0 / W, scale_dev=scale)
+            self._lagging = True
+            if self.step_count % LAZY_HIST == 0 and not self.in_graph:
+                self.flush_table()
+        elif sg is not None:
+            ops.adam_rows(self.table, self.t_m, self.t_v, sg.rows, sg.row_slot, self.step_count, lr, 1.0 / W, self.betas,
+                          self.eps, self.weight_decay, scale_dev=scale)
+        elif g_dense is not None:
+            ops.adam_rows(self.table, self.t_m, self.t_v, g_dense, None, self.step_count, lr, 1.0 / W, self.betas, self.eps,
+                          self.weight_decay, scale_dev=scale)
+
     # ---- lazy table update -------------------------------------------------------------------
     def _push_consts(self, step, lr, ctrl=None):
         """The step's Adam constants (and, for a replayed step, the control block) into the device-side history: one
@@ -387,13 +474,14 @@ class FusedAdamW:
             if len(evs) > 3:
                 evs.pop(0).synchronize()
 
-    def _lazy_call(self, mode, ids, grad_rows, row_slot, grad_scale, step=None):
+    def _lazy_call(self, mode, ids, grad_rows, row_slot, grad_scale, step=None, scale_dev=None):
         t = self.table
         sd = self.step_dev if (self.in_graph and mode != 2) else None     # captured launches read the step from the device
-        ops._timed_call("mhr_adam_rows_lazy", t.data_ptr(), self.t_m.data_ptr(), self.t_v.data_ptr(), t.shape[0], t.shape[1],
+        name, clip = ("mhr_adam_rows_lazy", ()) if scale_dev is None else ("mhr_adam_rows_lazy_scaled", (scale_dev.data_ptr(),))
+        ops._timed_call(name, t.data_ptr(), self.t_m.data_ptr(), self.t_v.data_ptr(), t.shape[0], t.shape[1],
                  ops._ptr(ids), 0 if ids is None else ids.numel(), ops._ptr(grad_rows), ops._ptr(row_slot),
                  self.last_step.data_ptr(), self.hist.data_ptr(), LAZY_HIST, self.step_count if step is None else step,
-                 float(grad_scale), self.betas[0], self.betas[1], self.eps, mode, ops._ptr(sd), ops._stream())
+                 float(grad_scale), self.betas[0], self.betas[1], self.eps, mode, ops._ptr(sd), *clip, ops._stream())
 
     def catch_up(self, ids):
         """Bring the rows of `ids` (int64, duplicates allowed) up to the last optimizer step before they are read."""
