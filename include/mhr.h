@@ -173,6 +173,23 @@ int mhr_adam_rows_lazy_scaled(float* w, float* m, float* v, int64_t n_rows, int 
                               int hist_len, int step, float grad_scale, float beta1, float beta2, float eps, int mode,
                               const int64_t* step_dev, const float* scale_dev, void* stream);
 
+/* mhr_adam_flat with parameter groups (the reference's `lr_mult_prefix` / `lr_mult_rate`, trainer.py:268-291): the same
+ * streaming update, bitwise what mhr_adam_flat gives each segment when run on it alone with the segment's group's lr and
+ * weight decay - but ONE launch over the whole buffer.  n % 8 == 0.  Static tables in device memory, built once by the caller:
+ *   seg_off [n_seg + 1] int64: ascending element offsets, seg_off[0] = 0, seg_off[n_seg] = n, every one a multiple of 8;
+ *   seg_group [n_seg] int32 in [0, n_groups);
+ *   chunk_seg [ceil(n / 8192)] int32: the segment that holds element c * 8192 (a workgroup owns whole 8192-element chunks
+ *     and walks the segments inside its chunk from there: no search).
+ * Per-step constants: gconst [hist_len, n_groups, 4] f32, row (step % hist_len, group) as mhr_adam_consts fills it for the
+ * group's lr and weight decay; the kernel ALWAYS reads them there.  step comes from the argument (>= 1) or, when step_dev
+ * (device int64[1]) is given, from step_dev[0] (hipGraph-replayed steps).  scale_dev (optional, device float[2], the record
+ * of mhr_grad_clip_coef): the gradient scale is scale_dev[1] instead of grad_scale.  n_groups in 1..16.  No atomics. */
+int mhr_adam_flat_groups(float* w, const float* g, float* m, float* v, int64_t n, float grad_scale,
+                         float beta1, float beta2, float eps, int step, void* w_bf16,
+                         const int64_t* seg_off, const int32_t* seg_group, int n_seg, const int32_t* chunk_seg,
+                         const float* gconst, int hist_len, int n_groups,
+                         const int64_t* step_dev, const float* scale_dev, void* stream);
+
 /* out[c] += sum_r x[r, c]: x bf16 [rows, cols] (cols % 8 == 0), out fp32 [cols].  The reduction of split-K weight-gradient
  * partials and of bias gradients straight into the flat gradient buffer (autograd's accumulate semantics: the caller
  * zeroes the buffer once per step).  Many-row inputs are reduced by several workgroups meeting through float atomics. */

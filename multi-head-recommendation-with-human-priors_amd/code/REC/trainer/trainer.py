@@ -327,8 +327,18 @@ class Trainer(object):
         # lazy table update: only the rows a step touches are written, the gradient-free steps of the others are replayed
         # when they are next read (bitwise the dense result; `lazy_table_adam: False` restores the dense pass per step)
         lazy = self.config.get('lazy_table_adam', True) and not getattr(model, "dense_embedding_grad", False)
+        # `lr_mult_prefix` / `lr_mult_rate` (reference trainer.py:268-291): parameters whose name starts with one of the prefixes
+        # train at learning_rate * lr_mult_rate, under the same schedule and weight decay; both keys truthy, as the reference asks
+        groups = None
+        prefixes, rate = self.config.get('lr_mult_prefix'), self.config.get('lr_mult_rate')
+        if prefixes and rate:
+            groups =[{"prefixes": list(prefixes), "lr_ratio": float(rate), "weight_decay": None}]
+            self.logger.info(f"Use higher lr rate {rate} x {self.optim_args['learning_rate']} for prefix {prefixes}")
+            for n, _ in model.named_parameters():
+                if any(n.startswith(x) for x in prefixes):
+                    self.logger.info(f"high lr param: {n} {self.optim_args['learning_rate'] * rate}")
         self.optimizer = FusedAdamW(model, lr=self.optim_args['learning_rate'], weight_decay=self.optim_args['weight_decay'],
-                                    lazy_table=bool(lazy), clip_grad_norm=self.config.get('clip_grad_norm'))
+                                    lazy_table=bool(lazy), clip_grad_norm=self.config.get('clip_grad_norm'), param_groups=groups)
         self._micro_step = 0
         if self.accumulate_grad == 1 and hasattr(self.optimizer, "enable_partial_arena"):
             self.optimizer.enable_partial_arena(True)     # one backward per step: all split-K partials summed by one launch

@@ -850,3 +850,116 @@ extern "C" int mhr_adam_flat_scaled(float* w, const float* g, float* m, float* v
   return adam_flat_launch(w, g, m, v, n, grad_scale, lr, beta1, beta2, eps, weight_decay, step, w_bf16, hist, hist_len,
                           step_dev, scale_dev, stream);
 }
+
+// ------------------------------------------------------------------------------------------
+// The flat update with parameter groups (the reference's `lr_mult_prefix` / `lr_mult_rate`, trainer.py:268-291): the same
+// stream over (w, g, m, v[, bf16 shadow]) through the same adam_update4, but decay_mul / step_size / inv_sqrt_bc2 belong to
+// the SEGMENT of the flat buffer an element lies in.  seg_off[S + 1] (ascending, multiples of 8, seg_off[S] = n) and
+// seg_group[S] are static; chunk_seg[c] names the segment that holds element c * AG_CHUNK, so a workgroup - which owns whole
+// chunks, like sqnorm_flat_kernel - starts there and walks forward: no search.  The constants of a piece (segment cut to the
+// chunk) are wave-uniform loads from gconst[step % hist_len][group].  No atomics: a pure function of the inputs.
+// ------------------------------------------------------------------------------------------
+#define AG_CHUNK 8192            // fp32 elements one workgroup owns at a time (= GN_CHUNK of grad_norm.hip)
+#define AG_BLOCK 256
+#define AG_MAX_GROUPS 16
+
+struct AdamGroups {
+  float beta1, beta2, one_m_beta1, one_m_beta2, eps, grad_scale;
+  int hist_len, n_groups, n_seg, step;
+};
+
+__device__ __forceinline__ void adam_groups_vec(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, bf16_t* __restrict__ w16, int64_t i, const AdamConst& cs) {
+  f32x4 wv = *reinterpret_cast<const f32x4*>(w + i), mv = *reinterpret_cast<const f32x4*>(m + i);
+  f32x4 vv = *reinterpret_cast<const f32x4*>(v + i);
+  const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
+  adam_update4(wv, mv, vv, gv, cs);
+  *reinterpret_cast<f32x4*>(w + i) = wv;
+  *reinterpret_cast<f32x4*>(m + i) = mv;
+  *reinterpret_cast<f32x4*>(v + i) = vv;
+  if (w16) Vec4IO<bf16_t>::store(w16 + i, wv);
+}
+
+__global__ __launch_bounds__(AG_BLOCK) void adam_flat_groups_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                                    float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                                    bf16_t* __restrict__ w16,
+                                                                    const int64_t* __restrict__ seg_off,
+                                                                    const int32_t* __restrict__ seg_group,
+                                                                    const int32_t* __restrict__ chunk_seg, int64_t n_chunks,
+                                                                    const float* __restrict__ gconst, AdamGroups a,
+                                                                    const int64_t* __restrict__ step_dev,
+                                                                    const float* __restrict__ scale_dev) {
+  if (scale_dev) a.grad_scale = scale_dev[1];   // clipped step: the whole gradient scale from the device (mhr_grad_clip_coef)
+  int64_t step = step_dev ? step_dev[0] : (int64_t)a.step;     // one path for host-issued and replayed steps
+  if (step < 0) step = 0;
+  const float* __restrict__ row = gconst + (step % a.hist_len) * (int64_t)a.n_groups * 4;
+  AdamConst cs;
+  cs.beta1 = a.beta1; cs.beta2 = a.beta2; cs.one_m_beta1 = a.one_m_beta1; cs.one_m_beta2 = a.one_m_beta2; cs.eps = a.eps;
+  cs.grad_scale = a.grad_scale;
+  constexpr int64_t STRIDE = (int64_t)AG_BLOCK * 4;            // elements one pass of the workgroup covers
+  for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const int64_t begin = c * AG_CHUNK;
+    const int64_t end = begin + AG_CHUNK < n ? begin + AG_CHUNK : n;
+    int s = chunk_seg[c];
+    if (s < 0) s = 0;
+    int64_t pos = begin;
+    while (pos < end && s < a.n_seg) {          // (s only grows and is bounded: the walk ends whatever the tables hold)
+      const int64_t s_end = seg_off[s + 1];
+      if (s_end <= pos) { ++s; continue; }      // an empty segment, or the chunk's first segment ends exactly here
+      const int64_t piece_end = s_end < end ? s_end : end;
+      int grp = seg_group[s];
+      grp = grp < 0 ? 0 : (grp >= a.n_groups ? a.n_groups - 1 : grp);
+      const float* __restrict__ h = row + grp * 4;
+      cs.decay_mul = h[0]; cs.step_size = h[1]; cs.inv_sqrt_bc2 = h[2];
+      int64_t i = pos + (int64_t)threadIdx.x * 4;
+      for (; i + 3 * STRIDE < piece_end; i += 4 * STRIDE) {    // four independent 16-byte loads per array in flight
+        f32x4 wv[4], mv[4], vv[4], gv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          wv[k] = *reinterpret_cast<const f32x4*>(w + i + k * STRIDE);
+          gv[k] = *reinterpret_cast<const f32x4*>(g + i + k * STRIDE);
+          mv[k] = *reinterpret_cast<const f32x4*>(m + i + k * STRIDE);
+          vv[k] = *reinterpret_cast<const f32x4*>(v + i + k * STRIDE);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          adam_update4(wv[k], mv[k], vv[k], gv[k], cs);
+          *reinterpret_cast<f32x4*>(w + i + k * STRIDE) = wv[k];
+          *reinterpret_cast<f32x4*>(m + i + k * STRIDE) = mv[k];
+          *reinterpret_cast<f32x4*>(v + i + k * STRIDE) = vv[k];
+          if (w16) Vec4IO<bf16_t>::store(w16 + i + k * STRIDE, wv[k]);
+        }
+      }
+      for (; i < piece_end; i += STRIDE) adam_groups_vec(w, g, m, v, w16, i, cs);    // (piece_end - pos is a multiple of 8)
+      pos = piece_end;
+      if (pos == s_end) ++s;
+    }
+  }
+}
+
+extern "C" int mhr_adam_flat_groups(float* w, const float* g, float* m, float* v, int64_t n, float grad_scale, float beta1,
+                                    float beta2, float eps, int step, void* w_bf16, const int64_t* seg_off,
+                                    const int32_t* seg_group, int n_seg, const int32_t* chunk_seg, const float* gconst,
+                                    int hist_len, int n_groups, const int64_t* step_dev, const float* scale_dev, void* stream) {
+  MHR_REQUIRE(w && g && m && v, "adam_flat_groups: null pointer (w / g / m / v)");
+  MHR_REQUIRE(seg_off && seg_group && chunk_seg, "adam_flat_groups: null pointer (seg_off / seg_group / chunk_seg)");
+  MHR_REQUIRE(gconst, "adam_flat_groups: null pointer (gconst)");
+  MHR_REQUIRE(n >= 0 && n % 8 == 0, "adam_flat_groups: n=%lld must be a non-negative multiple of 8", (long long)n);
+  MHR_REQUIRE(n_seg >= 1, "adam_flat_groups: n_seg=%d must be at least 1", n_seg);
+  MHR_REQUIRE(n_groups >= 1 && n_groups <= AG_MAX_GROUPS, "adam_flat_groups: n_groups=%d outside 1..%d", n_groups, AG_MAX_GROUPS);
+  MHR_REQUIRE(hist_len >= 1, "adam_flat_groups: hist_len=%d must be at least 1", hist_len);
+  MHR_REQUIRE(step_dev || step >= 1, "adam_flat_groups: step=%d must be at least 1 when step_dev is null", step);
+  MHR_REQUIRE(!w_bf16 || (uintptr_t)w_bf16 % 8 == 0, "adam_flat_groups: w_bf16 (the bf16 shadow) must be 8-byte aligned");
+  MHR_REQUIRE(((uintptr_t)w % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0),
+              "adam_flat_groups: w / g / m / v must be 16-byte aligned");
+  if (n == 0) return MHR_OK;
+  AdamGroups a;
+  a.beta1 = beta1; a.beta2 = beta2; a.one_m_beta1 = 1.0f - beta1; a.one_m_beta2 = 1.0f - beta2; a.eps = eps;
+  a.grad_scale = grad_scale; a.hist_len = hist_len; a.n_groups = n_groups; a.n_seg = n_seg; a.step = step;
+  const int64_t n_chunks = (n + AG_CHUNK - 1) / AG_CHUNK;
+  const int grid = (int)(n_chunks < 4096 ? n_chunks : 4096);
+  hipLaunchKernelGGL(adam_flat_groups_kernel, dim3(grid), dim3(AG_BLOCK), 0, (hipStream_t)stream, w, g, m, v, n,
+                     (bf16_t*)w_bf16, seg_off, seg_group, chunk_seg, n_chunks, gconst, a, step_dev, scale_dev);
+  MHR_CHECK_LAUNCH("adam_flat_groups");
+  return MHR_OK;
+}

@@ -208,6 +208,86 @@ def adam_flat(w, g, m, v, step, lr, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8
              _ptr(step_dev), _stream())
 
 
+ADAM_CHUNK = 8192         # elements of the flat buffer one workgroup of mhr_adam_flat_groups owns at a time (AG_CHUNK)
+ADAM_MAX_GROUPS = 16
+
+
+def adam_group_segments(sizes, groups, pad=8):
+    """Host side of the static tables of `adam_flat_groups`, as plain lists: parameters of `sizes[i]` elements laid out back to
+    back, each slot padded to `pad`, the whole buffer to 8; `groups[i]` the group of parameter i.  Consecutive parameters of one
+    group merge into one segment (the closing padding belongs to the last one).  -> (seg_off [S + 1], seg_group [S],
+    chunk_seg [ceil(n / 8192)]); an empty buffer has one empty segment of group 0."""
+    assert len(sizes) == len(groups) and pad % 8 == 0
+    seg_off, seg_group, off = [0], [], 0
+    for sz, gr in zip(sizes, groups):
+        if not seg_group or seg_group[-1] != int(gr):
+            if seg_group:
+                seg_off.append(off)
+            seg_group.append(int(gr))
+        off += (int(sz) + pad - 1) // pad * pad
+    if not seg_group:
+        seg_group.append(0)
+    seg_off.append((off + 7) // 8 * 8)
+    return seg_off, seg_group, adam_chunk_segments(seg_off)
+
+
+def adam_chunk_segments(seg_off):
+    """chunk_seg[c] = the segment that holds element c * 8192 (the last segment that starts at or before it and is not empty)."""
+    n, out, s = seg_off[-1], [], 0
+    for c in range((n + ADAM_CHUNK - 1) // ADAM_CHUNK):
+        while seg_off[s + 1] <= c * ADAM_CHUNK:
+            s += 1
+        out.append(s)
+    return out
+
+
+AdamGroupTables = collections.namedtuple("AdamGroupTables", "seg_off seg_group chunk_seg n n_seg n_groups")
+
+
+def adam_group_tables(seg_off, seg_group, n_groups, device):
+    """The static tables of `adam_flat_groups` on the device, checked on the host first (the kernel trusts them): ascending
+    offsets from 0 that are multiples of 8, groups in [0, n_groups), 1 <= n_groups <= 16."""
+    seg_off, seg_group = [int(x) for x in seg_off], [int(x) for x in seg_group]
+    if len(seg_group) < 1 or len(seg_off) != len(seg_group) + 1 or seg_off[0] != 0:
+        raise ValueError("adam_group_tables: seg_off must hold len(seg_group) + 1 >= 2 offsets and start at 0")
+    if any(o % 8 for o in seg_off) or any(b < a for a, b in zip(seg_off, seg_off[1:])):
+        raise ValueError("adam_group_tables: seg_off must ascend in multiples of 8")
+    if not 1 <= n_groups <= ADAM_MAX_GROUPS or any(not 0 <= x < n_groups for x in seg_group):
+        raise ValueError(f"adam_group_tables: n_groups={n_groups} outside 1..{ADAM_MAX_GROUPS}, or a segment's group outside [0, n_groups)")
+    chunk_seg = adam_chunk_segments(seg_off)
+    return AdamGroupTables(torch.tensor(seg_off, dtype=torch.int64, device=device),
+                           torch.tensor(seg_group, dtype=torch.int32, device=device),
+                           torch.tensor(chunk_seg or [0], dtype=torch.int32, device=device),
+                           seg_off[-1], len(seg_group), int(n_groups))
+
+
+def adam_group_consts(out_row, step, lrs, weight_decays, betas=(0.9, 0.999), eps=1e-8):
+    """out_row (HOST fp32 [n_groups, 4], contiguous) = one `mhr_adam_consts` row per group: the constants of step `step`."""
+    assert not out_row.is_cuda and out_row.dtype == torch.float32 and out_row.is_contiguous()
+    assert out_row.shape == (len(lrs), 4) and len(lrs) == len(weight_decays)
+    for k, (lr, wd) in enumerate(zip(lrs, weight_decays)):
+        lib.call("mhr_adam_consts", float(lr), betas[0], betas[1], eps, float(wd), int(step), out_row[k].data_ptr())
+    return out_row
+
+
+def adam_flat_groups(w, g, m, v, tables, gconst, step, grad_scale=1.0, betas=(0.9, 0.999), eps=1e-8, w_bf16=None,
+                     step_dev=None, scale_dev=None):
+    """`adam_flat` with per-segment lr / weight decay in ONE launch (mhr_adam_flat_groups).  tables: `adam_group_tables`;
+    gconst: device fp32 [hist_len, n_groups, 4], row step % hist_len filled by `adam_group_consts`; the kernel always reads its
+    constants there - `step` (or step_dev[0], device int64, for a hipGraph-replayed step) only picks the row."""
+    _chk(gconst, "gconst", torch.float32)
+    if gconst.dim() != 3 or gconst.shape[1] != tables.n_groups or gconst.shape[2] != 4:
+        raise ValueError(f"adam_flat_groups: gconst must be [hist_len, {tables.n_groups}, 4], got {tuple(gconst.shape)}")
+    if w.numel() != tables.n or any(t.numel() != w.numel() for t in (g, m, v)) or (w_bf16 is not None and w_bf16.numel() != w.numel()):
+        raise ValueError(f"adam_flat_groups: the tables cover {tables.n} elements, the buffers hold {w.numel()}")
+    for t, name in ((w, "w"), (g, "g"), (m, "m"), (v, "v")):
+        _chk(t, name, torch.float32)
+    _timed_call("mhr_adam_flat_groups", w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), grad_scale,
+                betas[0], betas[1], eps, int(step), _ptr(w_bf16), tables.seg_off.data_ptr(), tables.seg_group.data_ptr(),
+                tables.n_seg, tables.chunk_seg.data_ptr(), gconst.data_ptr(), gconst.shape[0], tables.n_groups,
+                _ptr(step_dev), _ptr(scale_dev), _stream())
+
+
 def grad_sqnorm_partials(n, dim=1):
     """How many fp64 partials `grad_sqnorm_flat` over n elements (dim = 1) / `grad_sqnorm_rows` over n rows of `dim` writes
     (a host size query; 1 at n = 0)."""

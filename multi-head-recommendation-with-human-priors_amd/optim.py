@@ -54,8 +54,16 @@ LAZY_HIST = 64        # steps a table row may lag behind before everything is fl
 
 
 class FusedAdamW:
-    def __init__(self, model, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, lazy_table=False, clip_grad_norm=None):
-        """clip_grad_norm (None or <= 0: off, exactly the unclipped step): clip the gradient by its global L2 norm over every
+    def __init__(self, model, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, lazy_table=False, clip_grad_norm=None,
+                 param_groups=None):
+        """param_groups (None: exactly the ungrouped optimizer): a list of {"prefixes": [...], "lr_ratio": float, "weight_decay":
+        float | None} - the reference's `lr_mult_prefix` / `lr_mult_rate` parameter groups (trainer.py:268-291).  Group 0 is
+        implicit (ratio 1, the constructor's weight_decay); a parameter joins the FIRST listed group one of whose prefixes its
+        `named_parameters()` name starts with.  The flat layout does not change: consecutive parameters of one group form a
+        segment and ONE launch (`mhr_adam_flat_groups`) updates the buffer with per-segment constants.  The lr of group g in a
+        step is `param_groups[0]["lr"] * lr_ratio_g` (a LambdaLR schedule scales every group alike); only entry 0's lr is an
+        input, the others are written back at the step for logging.  The item table belongs to the group its name matches.
+        clip_grad_norm (None or <= 0: off, exactly the unclipped step): clip the gradient by its global L2 norm over every
         trainable parameter (torch.nn.utils.clip_grad_norm_; the reference's `clip_grad_norm`, trainer.py:99).  The norm is
         reduced on the device and the Adam kernels read the resulting scale from device memory (`_clip_state`): no host read, so
         a clipped step replays from a hipGraph like any other.  `grad_norm` (device fp32 scalar) holds the last step's pre-clip
@@ -118,6 +126,9 @@ class FusedAdamW:
             p._mhr_opt = None                                            # set by enable_partial_arena()
             off += sz
         self.param_groups = [{"lr": lr}]                                 # scheduler-facing view
+        self.groups = None                                               # [{"lr_ratio", "weight_decay", "names"}], group 0 first
+        if param_groups is not None:
+            self._build_groups(param_groups, names, sizes)
         self.lazy = bool(lazy_table) and self.table is not None and os.environ.get("MHR_LAZY_ADAM", "1") != "0"
         # per-step constants (lr decay, bias corrections) of the last LAZY_HIST steps on the device: the lazy table replay
         # reads them, and so does every Adam kernel of a step replayed from a hipGraph (`step_dev`, set by the Trainer's
@@ -125,10 +136,24 @@ class FusedAdamW:
         # Row LAZY_HIST of the same buffer carries the replay control block (two int64: dropout step counter, optimizer step),
         # so ONE small host-to-device copy per step refreshes everything a replayed step reads.  The copy's source is a slot
         # of a pinned ring: an asynchronous copy reads host memory when the DMA runs, not when it is issued.
-        self.hist = torch.zeros(LAZY_HIST + 1, 4, dtype=torch.float32, device=dev)
+        if self.groups is None:
+            self.hist = torch.zeros(LAZY_HIST + 1, 4, dtype=torch.float32, device=dev)
+            self._hist_host = torch.zeros(LAZY_HIST + 1, 4, dtype=torch.float32)
+            self._hist_ring = torch.zeros(HOST_RING, LAZY_HIST + 1, 4, dtype=torch.float32)
+            self._consts_dev, self._consts_host = self.hist, self._hist_host           # what the upload copies
+        else:
+            # with groups the same upload also carries gconst [LAZY_HIST, n_groups, 4] (one mhr_adam_consts row per step and
+            # group, read by mhr_adam_flat_groups) behind hist + control block: one buffer, still ONE small copy per step.
+            # `hist` keeps its shape and meaning: the TABLE's constants (its group's lr and weight decay) and the control block.
+            n_h, n_g = (LAZY_HIST + 1) * 4, LAZY_HIST * len(self.groups) * 4
+            self._consts_dev = torch.zeros(n_h + n_g, dtype=torch.float32, device=dev)
+            self._consts_host = torch.zeros(n_h + n_g, dtype=torch.float32)
+            self.hist, self.gconst = self._consts_dev[:n_h].view(LAZY_HIST + 1, 4), self._consts_dev[n_h:].view(LAZY_HIST, -1, 4)
+            self._hist_host = self._consts_host[:n_h].view(LAZY_HIST + 1, 4)
+            self._gconst_host = self._consts_host[n_h:].view(LAZY_HIST, -1, 4)
+            self._hist_ring = torch.zeros(HOST_RING, n_h + n_g, dtype=torch.float32)
+            self._seg = ops.adam_group_tables(self._seg_lists[0], self._seg_lists[1], len(self.groups), dev)
         self.ctrl = self.hist[LAZY_HIST].view(torch.int64)               # device int64[2]
-        self._hist_host = torch.zeros(LAZY_HIST + 1, 4, dtype=torch.float32)
-        self._hist_ring = torch.zeros(HOST_RING, LAZY_HIST + 1, 4, dtype=torch.float32)
         if dev.type == "cuda":
             self._hist_ring = self._hist_ring.pin_memory()
         self._n_push = 0
@@ -150,6 +175,67 @@ class FusedAdamW:
             self._clip_partials = torch.zeros(self._clip_p_flat + n_tab, dtype=torch.float64, device=dev)
             self._clip_state = torch.zeros(2, dtype=torch.float32, device=dev)
             self.grad_norm = self._clip_state[0]
+
+    # ---- parameter groups -----------------------------------------------------------------------
+    def _build_groups(self, param_groups, names, sizes):
+        """Assign every parameter (the flat ones in layout order, and the item table) to its group and lay the segments of the
+        flat buffer out (`ops.adam_group_segments`).  Nothing is reordered."""
+        specs = [{"prefixes": [], "lr_ratio": 1.0, "weight_decay": self.weight_decay}]
+        for k, gr in enumerate(param_groups):
+            unknown = set(gr) - {"prefixes", "lr_ratio", "weight_decay"}
+            if unknown or "prefixes" not in gr or "lr_ratio" not in gr:
+                raise ValueError(f"param_groups[{k}]: expected {{'prefixes', 'lr_ratio'[, 'weight_decay']}}, got {sorted(gr)}")
+            wd = gr.get("weight_decay")
+            specs.append({"prefixes": [str(x) for x in gr["prefixes"]], "lr_ratio": float(gr["lr_ratio"]),
+                          "weight_decay": self.weight_decay if wd is None else float(wd)})
+        if len(specs) > ops.ADAM_MAX_GROUPS:
+            raise ValueError(f"param_groups: {len(specs)} groups with the implicit first one, at most {ops.ADAM_MAX_GROUPS}")
+
+        def group_of(name):
+            return next((k for k, s in enumerate(specs) if any(name.startswith(x) for x in s["prefixes"])), 0)
+
+        flat_groups = [group_of(n) for n in names]
+        self.groups = [{"lr_ratio": s["lr_ratio"], "weight_decay": s["weight_decay"], "names": []} for s in specs]
+        for n, k in zip(names, flat_groups):
+            self.groups[k]["names"].append(n)
+        self._table_group = 0
+        if self.table is not None:
+            t_name = next(n for n, p in self.model.named_parameters() if p is self.table)
+            self._table_group = group_of(t_name)
+            self.groups[self._table_group]["names"].append(t_name)
+        self._seg_lists = ops.adam_group_segments([p.numel() for p in self.dense], flat_groups, pad=self.pad)
+        assert self._seg_lists[0][-1] == (sum(sizes) + 7) // 8 * 8
+        lr = self.param_groups[0]["lr"]
+        self.param_groups = [{"lr": lr * g["lr_ratio"], "weight_decay": g["weight_decay"], "lr_ratio": g["lr_ratio"],
+                              "names": list(g["names"])} for g in self.groups]
+
+    def _group_lrs(self, lr):
+        """The lr of every group in a step whose scheduled base lr is `lr` (Python floats), written back for logging."""
+        lrs = [lr * g["lr_ratio"] for g in self.groups]
+        for pg, x in zip(self.param_groups[1:], lrs[1:]):
+            pg["lr"] = x
+        return lrs
+
+    def _table_lr_wd(self, lr):
+        """(lr, weight decay) of the item table's update in a step whose base lr is `lr`."""
+        if self.groups is None:
+            return lr, self.weight_decay
+        g = self.groups[self._table_group]
+        return lr * g["lr_ratio"], g["weight_decay"]
+
+    def _adam_flat(self, lr, grad_scale, scale_dev=None):
+        """The flat update of this step: `mhr_adam_flat[_scaled]`, or with groups `mhr_adam_flat_groups`, whose constants
+        `_push_consts` has put (or, for a replayed step, `begin_replayed_step` puts) into `gconst`."""
+        sd = self.step_dev if self.in_graph else None
+        if self.groups is None:
+            ops.adam_flat(self.flat_w, self.flat_g, self.flat_m, self.flat_v, self.step_count, lr, grad_scale, self.betas,
+                          self.eps, self.weight_decay, w_bf16=self.flat_w16, hist=self.hist if sd is not None else None,
+                          step_dev=sd, scale_dev=scale_dev)
+            return
+        if not self.in_graph:
+            self._push_consts(self.step_count, lr)
+        ops.adam_flat_groups(self.flat_w, self.flat_g, self.flat_m, self.flat_v, self._seg, self.gconst, self.step_count,
+                             grad_scale, self.betas, self.eps, w_bf16=self.flat_w16, step_dev=sd, scale_dev=scale_dev)
 
     # ---- split-K partials of ALL weight gradients in one arena, reduced by ONE launch at the step -------------------------
     def enable_partial_arena(self, on=True):
@@ -345,25 +431,24 @@ class FusedAdamW:
             self.model.begin_sparse_exchange()
         if dense_work is not None:
             dense_work.wait()
-        sd = self.step_dev if self.in_graph else None
-        ops.adam_flat(self.flat_w, self.flat_g, self.flat_m, self.flat_v, self.step_count, lr, 1.0 / W, self.betas, self.eps,
-                      self.weight_decay, w_bf16=self.flat_w16, hist=self.hist if sd is not None else None, step_dev=sd)
+        self._adam_flat(lr, 1.0 / W)
         for p in self.dense:
             if hasattr(p, "_mhr_bf16"):
                 p._mhr_ver = p._version
         if self.table is None:
             return
         sg = self.model.finish_sparse_grad() if hasattr(self.model, "finish_sparse_grad") else self.model.sparse_grad
-        if self.lazy and not self.in_graph:          # every step has its constants in the history, with or without a gradient
-            self._push_consts(self.step_count, lr)   # (a captured step gets them from begin_replayed_step at every replay)
+        if self.lazy and not self.in_graph and self.groups is None:   # every step has its constants in the history, with or
+            self._push_consts(self.step_count, lr)   # without a gradient (a captured step gets them from begin_replayed_step at
+        t_lr, t_wd = self._table_lr_wd(lr)           # every replay; with groups `_adam_flat` has uploaded them already)
         if sg is not None and self.lazy:
             self._lazy_call(1, sg.sorted_ids, sg.rows, sg.row_slot, 1.0 / W)
             self._lagging = True
             if self.step_count % LAZY_HIST == 0 and not self.in_graph:   # nobody lags further than the history reaches
                 self.flush_table()
         elif sg is not None:
-            ops.adam_rows(self.table, self.t_m, self.t_v, sg.rows, sg.row_slot, self.step_count, lr, 1.0 / W, self.betas,
-                          self.eps, self.weight_decay)
+            ops.adam_rows(self.table, self.t_m, self.t_v, sg.rows, sg.row_slot, self.step_count, t_lr, 1.0 / W, self.betas,
+                          self.eps, t_wd)
         elif self.table.grad is not None:                                # dense_embedding_grad mode
             g = self.table.grad
             if self.lazy:                      # a dense step in between lazy ones: everything up to date first, and after it
@@ -372,8 +457,7 @@ class FusedAdamW:
                 self.step_count += 1
                 self.last_step.fill_(self.step_count)
             D.allreduce_mean_(g)
-            ops.adam_rows(self.table, self.t_m, self.t_v, g, None, self.step_count, lr, 1.0, self.betas, self.eps,
-                          self.weight_decay)
+            ops.adam_rows(self.table, self.t_m, self.t_v, g, None, self.step_count, t_lr, 1.0, self.betas, self.eps, t_wd)
 
     # ---- the step with gradient clipping --------------------------------------------------------
     def _clip_room(self, need):
@@ -419,28 +503,26 @@ class FusedAdamW:
         elif g_dense is not None:
             n_p += ops.grad_sqnorm_flat(g_dense.view(-1), self._clip_partials, n_p)
         scale = ops.grad_clip_coef(self._clip_partials, n_p, 1.0 / W, self.clip_grad_norm, self._clip_state)
-        sd = self.step_dev if self.in_graph else None
-        ops.adam_flat(self.flat_w, self.flat_g, self.flat_m, self.flat_v, self.step_count, lr, 1.0 / W, self.betas, self.eps,
-                      self.weight_decay, w_bf16=self.flat_w16, hist=self.hist if sd is not None else None, step_dev=sd,
-                      scale_dev=scale)
+        self._adam_flat(lr, 1.0 / W, scale_dev=scale)
         for p in self.dense:
             if hasattr(p, "_mhr_bf16"):
                 p._mhr_ver = p._version
         if self.table is None:
             return
-        if self.lazy and not self.in_graph:
+        if self.lazy and not self.in_graph and self.groups is None:
             self._push_consts(self.step_count, lr)
+        t_lr, t_wd = self._table_lr_wd(lr)
         if sg is not None and self.lazy:
             self._lazy_call(1, sg.sorted_ids, sg.rows, sg.row_slot, 1.0 / W, scale_dev=scale)
             self._lagging = True
             if self.step_count % LAZY_HIST == 0 and not self.in_graph:
                 self.flush_table()
         elif sg is not None:
-            ops.adam_rows(self.table, self.t_m, self.t_v, sg.rows, sg.row_slot, self.step_count, lr, 1.0 / W, self.betas,
-                          self.eps, self.weight_decay, scale_dev=scale)
+            ops.adam_rows(self.table, self.t_m, self.t_v, sg.rows, sg.row_slot, self.step_count, t_lr, 1.0 / W, self.betas,
+                          self.eps, t_wd, scale_dev=scale)
         elif g_dense is not None:
-            ops.adam_rows(self.table, self.t_m, self.t_v, g_dense, None, self.step_count, lr, 1.0 / W, self.betas, self.eps,
-                          self.weight_decay, scale_dev=scale)
+            ops.adam_rows(self.table, self.t_m, self.t_v, g_dense, None, self.step_count, t_lr, 1.0 / W, self.betas, self.eps,
+                          t_wd, scale_dev=scale)
 
     # ---- lazy table update -------------------------------------------------------------------
     def _push_consts(self, step, lr, ctrl=None):
@@ -448,15 +530,19 @@ class FusedAdamW:
         asynchronous copy from a pinned ring slot, no host stall."""
         from . import lib
         row = step % LAZY_HIST
-        lib.call("mhr_adam_consts", float(lr), self.betas[0], self.betas[1], self.eps, self.weight_decay, int(step),
+        t_lr, t_wd = self._table_lr_wd(lr)                               # `hist`: the constants of the table's update
+        lib.call("mhr_adam_consts", float(t_lr), self.betas[0], self.betas[1], self.eps, t_wd, int(step),
                  self._hist_host[row].data_ptr())
+        if self.groups is not None:                                      # `gconst`: one row per group, the same upload
+            ops.adam_group_consts(self._gconst_host[row], step, self._group_lrs(lr), [g["weight_decay"] for g in self.groups],
+                                  self.betas, self.eps)
         if ctrl is not None:
             c = self._hist_host[LAZY_HIST].view(torch.int64)
             c[0], c[1] = ctrl
         slot = self._hist_ring[self._n_push % HOST_RING]
         self._n_push += 1
-        slot.copy_(self._hist_host)
-        self.hist.copy_(slot, non_blocking=True)
+        slot.copy_(self._consts_host)
+        self._consts_dev.copy_(slot, non_blocking=True)
         self._throttle()
 
     def _throttle(self):
@@ -497,6 +583,9 @@ class FusedAdamW:
     def state_dict(self):
         self.flush_table()
         sd = {"step": self.step_count, "flat_m": self.flat_m, "flat_v": self.flat_v, "layout": self.layout, "pad": self.pad}
+        if self.groups is not None:      # a record, not state: the moments do not depend on it and loading ignores it
+            sd["groups"] = [{"lr_ratio": g["lr_ratio"], "weight_decay": g["weight_decay"], "names": list(g["names"])}
+                            for g in self.groups]
         if self.table is not None:
             sd.update(t_m=self.t_m, t_v=self.t_v)
         return sd
