@@ -887,6 +887,35 @@ int mhr_multihead_merge_dedup(const float* vals, const int64_t* idx, int B, int 
 int mhr_hit_matrix(const int64_t* topk_idx, int B, int k, const int64_t* positives, int pos_stride, int n_pos,
                    uint8_t* hit, void* stream);
 
+/* Streaming evaluation metrics (evaluator/metrics.py:29-41, 61-69, 93-101, 131-142, 179-181, 221-238, 262-263): the fp64 sums
+ * over users of the per-user metric curves at the cut-offs topk[t], added onto device accumulators - what the numpy metric
+ * classes form from the stored [users, K+1] matrices, without storing them.
+ *   per user b and pred index i (p = pred[i], n = pos_len[b, p] >= 1, ideal = min(n, K)), with hit[j] = topk_idx[b, j] occurs in
+ *   positives[b, 0:p+1] and c[j] its running count, the six columns at rank j = topk[t] - 1 are, in this order,
+ *     recall c[j] / n;  ndcg (sum_{i<=j, hit} disc[i]) / idcg[min(j, ideal - 1)];  hit c[j] > 0;  mrr 1 / (first hit rank) or 0;
+ *     map (sum_{i<=j} hit[i] c[i] / (i + 1)) / min(j + 1, ideal);  precision c[j] / (j + 1)
+ *   all in fp64, running sums in rank order (np.cumsum).  The user adds them to sums[i, g] and 1 to counts[i, g] for every
+ *   group g whose bit is set in group_bits[b, i].
+ *   entropy@k (once per user, no groups; item_tag_bits and entropy both NULL = off): cnt[c] = how many of the first k items
+ *   carry tag c < n_tags (bit c of item_tag_bits[item]; ids outside [0, n_items) carry none), p = cnt / sum(cnt),
+ *   value = -sum_{p>0} p log2 p.
+ * pred [n_pred] and topk [n_topk] are HOST arrays (read before the launch); disc[j] = 1 / log2(j + 2) and idcg = its running
+ * sum are device arrays [K] the caller makes once.  sums [n_pred, n_groups, 6, n_topk] f64, counts [n_pred, n_groups] i64,
+ * entropy [n_topk] f64: all +=.
+ * Limits (checked on the host before any launch): 1 <= K <= 2048, 1 <= n_pred <= 16, 1 <= n_topk <= 16 with every topk[t] in
+ * [1, K], 1 <= n_groups <= 32, n_tags <= 32, pos_stride and pos_len_stride > max(pred).
+ * No floating-point atomics: one wave per 64 users adds its users in user order into one partial per cell in `workspace`, a
+ * second kernel adds the partials in workgroup order onto the accumulators - the same launch sequence on the same inputs gives
+ * bit-identical accumulators.
+ *   mhr_eval_metric_sums_workspace_bytes: HOST size query, no launch:
+ *     ceil(B / 64) * (n_pred * n_groups * 6 * n_topk + n_topk + n_pred * n_groups) * 8 bytes; -1 outside the limits. */
+int64_t mhr_eval_metric_sums_workspace_bytes(int B, int n_pred, int n_groups, int n_topk);
+int mhr_eval_metric_sums(const int64_t* topk_idx, int B, int K, const int64_t* positives, int pos_stride,
+                         const int32_t* pos_len, int pos_len_stride, const int32_t* pred, int n_pred,
+                         const int32_t* topk, int n_topk, const double* disc, const double* idcg,
+                         const uint32_t* group_bits, int n_groups, const uint32_t* item_tag_bits, int64_t n_items,
+                         int n_tags, double* sums, int64_t* counts, double* entropy, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

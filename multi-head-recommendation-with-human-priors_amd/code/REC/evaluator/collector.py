@@ -4,11 +4,17 @@
 that `HSTU.predict_topk` returns.  The cross-head merge + first-occurrence dedup (reference collector.py:249-275:
 a [B,N] bool table and an H*K-step Python loop) and the hit matrix (collector.py:300-316) run in gfx950 kernels;
 everything stays on the device until the per-pred_len `[B, K+1]` result is appended.
+
+`stream_metrics: True` (default off) stores nothing per batch: one `eval_metric_sums` launch adds the batch's users onto a small
+fp64 accumulator on the device (the summed metric curves at `topk`, over all users and per category / outlier group), and
+`get_data_struct` hands the sums out as `'rec.metric_sums'` / `'rec.entropy_sums'` after one device->host copy.
 """
 import copy
 
 import numpy as np
 import torch
+
+from .metrics import COLUMNS
 
 
 class DataStruct(object):
@@ -66,12 +72,131 @@ class Collector(object):
             raise ValueError(f'Unknown head_interaction: {hi}')
         self.split_mode = config['split_mode']
         self.all_tags = None
+        self.stream_metrics = bool(config.get('stream_metrics', False))
+        if self.stream_metrics:
+            self._stream_init(config)
 
     def set_all_tags(self, item_tags):
         self.all_tags = item_tags
+        if self.stream_metrics:
+            self._tag_bits = self._pack_tag_bits(item_tags)
 
     def reset_all_tags(self):
         self.all_tags = None
+        if self.stream_metrics:
+            self._tag_bits = None
+
+    # ---- stream_metrics: running sums instead of stored per-batch tensors -----------------------------------------------------
+    def _stream_init(self, config):
+        """Group layout of the accumulator: bit 0 every user, bits 1..n_cats the target categories, the last bit the outlier
+        users (each only when the configuration evaluates it)."""
+        n_cats = config['eval_num_cats'] or 0
+        self._n_cats = n_cats if (n_cats > 1 and config.get('eval_by_cat', True)) else 0
+        self._outlier = config['outlier_user_metrics'] is not None
+        self.n_groups = 1 + self._n_cats + int(self._outlier)
+        from mhr_amd.ops import METRIC_LIMITS as lim_of                        # the limits of mhr_eval_metric_sums (mhr.h)
+        for what, n, lim in (('groups (1 + eval_num_cats + outlier)', self.n_groups, lim_of['n_groups']),
+                             ('len(metrics_pred_len_list)', len(self.metrics_pred_len_list), lim_of['n_pred']),
+                             ('len(topk)', len(self.topk), lim_of['n_topk']), ('max(topk)', max(self.topk), lim_of['K'])):
+            if not 1 <= n <= lim:
+                raise ValueError(f"stream_metrics: {what} = {n} is outside the kernel's limit [1, {lim}]")
+        if self._outlier and self.eval_pred_len - 1 not in self.metrics_pred_len_list:
+            raise ValueError("stream_metrics: outlier_user_metrics needs eval_pred_len - 1 in metrics_pred_len_list")
+        self._tag_bits = None
+        self._acc = None                 # device f64 words: sums [P, G, 6, T] | entropy [T] | counts [P, G] (int64 bits)
+        self._host = None                # the one device->host copy of an evaluation, handed out slice by slice
+        self._dirty = False
+        self._seen = dict(tags=False, cats=False, outlier=False)
+
+    def _pack_tag_bits(self, item_tags):
+        """[N, C'] tag table -> [N] words, bit c = the item carries tag c (int32 storage of the uint32 bit pattern)."""
+        C = item_tags.shape[1]
+        from mhr_amd.ops import METRIC_LIMITS
+        if C > METRIC_LIMITS['n_tags']:
+            raise ValueError(f"stream_metrics: {C} item tags exceed the kernel's limit of {METRIC_LIMITS['n_tags']}")
+        w = (item_tags != 0).long() << torch.arange(C, device=item_tags.device)
+        return self._low32(w.sum(dim=1)), C
+
+    @staticmethod
+    def _low32(words):
+        """int64 words in [0, 2^32) -> int32 storage of the same 32 bits."""
+        return torch.where(words >= 2 ** 31, words - 2 ** 32, words).int().contiguous()
+
+    def _stream_consts(self, dev):
+        """Per-device constants of the group words: the pred_len columns, the weight 2^(1 + c) of category c, and the outlier
+        weight 2^(G - 1) in the column of eval_pred_len - 1 (zero elsewhere)."""
+        c = self.__dict__.setdefault('_consts', {}).get(dev)
+        if c is None:
+            P, G = len(self.metrics_pred_len_list), self.n_groups
+            ow = torch.zeros(1, P, dtype=torch.int64)
+            if self._outlier:
+                ow[0, self.metrics_pred_len_list.index(self.eval_pred_len - 1)] = 2 ** (G - 1)
+            c = self._consts[dev] = dict(pred=torch.tensor(list(self.metrics_pred_len_list), device=dev),
+                                         cat_weight=(2 ** torch.arange(1, 1 + self._n_cats)).to(dev), outlier_weight=ow.to(dev))
+        return c
+
+    def _acc_views(self, buf):
+        P, G, T = len(self.metrics_pred_len_list), self.n_groups, len(self.topk)
+        n_sum = P * G * len(COLUMNS) * T
+        return buf[:n_sum].view(P, G, len(COLUMNS), T), buf[n_sum:n_sum + T], buf[n_sum + T:].view(torch.int64).view(P, G)
+
+    def _stream_collect(self, topk_idx, positive_i, pos_len_full, tag_category, outlier_users):
+        from mhr_amd import ops
+        dev, B = topk_idx.device, topk_idx.shape[0]
+        P, G, T = len(self.metrics_pred_len_list), self.n_groups, len(self.topk)
+        if positive_i.shape[1] <= max(self.metrics_pred_len_list):
+            raise ValueError(f"stream_metrics: positives hold {positive_i.shape[1]} targets, metrics_pred_len_list needs "
+                             f"{max(self.metrics_pred_len_list) + 1}")
+        if self._acc is None or self._acc.device != dev:
+            self._acc = torch.zeros(P * G * len(COLUMNS) * T + T + P * G, dtype=torch.float64, device=dev)
+        # group words [B, P]: a handful of small launches whatever the number of pred_lens (int64 arithmetic, then the low 32 bits)
+        consts = self._stream_consts(dev)
+        if tag_category is not None and self._n_cats:
+            seen = tag_category.to(dev)[:, :, :self._n_cats].ne(0).cumsum(dim=1).ne(0)        # any over targets [0 : e + 1]
+            bits = (seen.index_select(1, consts['pred']) * consts['cat_weight']).sum(dim=2) + 1
+            self._seen['cats'] = True
+        else:
+            bits = torch.ones(B, P, dtype=torch.int64, device=dev)
+        if outlier_users is not None and self._outlier:
+            bits = bits + outlier_users.to(dev).ne(0).long()[:, None] * consts['outlier_weight']
+            self._seen['outlier'] = True
+        bits = self._low32(bits)
+        sums, entropy, counts = self._acc_views(self._acc)
+        tag_bits, n_tags = (None, 0)
+        if self.all_tags is not None:
+            tag_bits, n_tags = self._tag_bits
+            tag_bits = tag_bits.to(dev)
+            self._tag_bits = (tag_bits, n_tags)
+            self._seen['tags'] = True
+        ops.eval_metric_sums(topk_idx.contiguous(), positive_i, pos_len_full, list(self.metrics_pred_len_list), list(self.topk),
+                             bits, G, sums, counts, item_tag_bits=tag_bits, n_tags=n_tags,
+                             entropy=entropy if tag_bits is not None else None)
+        self._dirty = True
+
+    def _stream_data_struct(self, pred_idx):
+        """The sums of one pred_len (or the shared entropy sums at -1) as host numpy; what is handed out is zeroed, as the
+        stored path deletes the keys it hands out."""
+        if self._dirty:
+            self._host = self._acc.cpu()                                   # the one device->host copy of the evaluation
+            self._acc.zero_()
+            self._dirty = False
+        out = DataStruct()
+        if self._host is None:
+            return out
+        sums, entropy, counts = self._acc_views(self._host)
+        if pred_idx == -1:
+            if self._seen['tags']:
+                out.set('rec.entropy_sums', entropy.numpy().copy())
+                entropy.zero_()
+                self._seen['tags'] = False
+            return out
+        i = self.metrics_pred_len_list.index(pred_idx)
+        out.set('rec.metric_sums', dict(sums=sums[i].numpy().copy(), counts=counts[i].numpy().copy(), n_cats=self._n_cats,
+                                        cats=self._seen['cats'],
+                                        outlier=self._seen['outlier'] and pred_idx == self.eval_pred_len - 1))
+        sums[i].zero_()
+        counts[i].zero_()
+        return out
 
     # ------------------------------------------------------------------------------------------
     def _decode(self, scores, top_k, detail):
@@ -113,10 +238,11 @@ class Collector(object):
     def eval_batch_collect(self, scores_tensor, positive_u, positive_i, tag_category=None, outlier_users=None,
                            log_detailed_results=False):
         from mhr_amd import ops
-        if tag_category is not None:
+        stored = not self.stream_metrics
+        if stored and tag_category is not None:
             for p in self.metrics_pred_len_list:
                 self.data_struct[p].update_tensor('rec.tgt_tags', torch.any(tag_category[:, :p + 1].bool(), dim=1))
-        if outlier_users is not None:
+        if stored and outlier_users is not None:
             self.data_struct[self.eval_pred_len - 1].update_tensor('rec.outlier_users', outlier_users)
         top_k = max(self.topk)
         detail = {} if log_detailed_results else None
@@ -124,16 +250,19 @@ class Collector(object):
         dev = topk_idx.device
         positive_i = positive_i.to(dev).contiguous()
         B = topk_idx.shape[0]
-        if self.all_tags is not None:
+        if stored and self.all_tags is not None:
             self.data_struct[-1].update_tensor('rec.rec_tags', self.all_tags.to(dev)[topk_idx])
         # distinct positives among the ascending-sorted targets (reference collector.py:301-304)
         srt, _ = positive_i.sort(dim=1)
         first = torch.ones_like(srt, dtype=torch.bool)
         first[:, 1:] = srt[:, 1:] != srt[:, :-1]
         pos_len_full = first.cumsum(dim=1).int()
-        for p in self.metrics_pred_len_list:
-            hit = ops.hit_matrix(topk_idx, positive_i, p + 1)                       # cumulative over [0 : p+1]
-            self.data_struct[p].update_tensor('rec.topk', torch.cat((hit.int(), pos_len_full[:, p:p + 1]), dim=1))
+        if stored:
+            for p in self.metrics_pred_len_list:
+                hit = ops.hit_matrix(topk_idx, positive_i, p + 1)                       # cumulative over [0 : p+1]
+                self.data_struct[p].update_tensor('rec.topk', torch.cat((hit.int(), pos_len_full[:, p:p + 1]), dim=1))
+        else:
+            self._stream_collect(topk_idx, positive_i, pos_len_full, tag_category, outlier_users)
         if log_detailed_results:
             out = {}
             for k_, v in detail.items():
@@ -142,6 +271,8 @@ class Collector(object):
         return {}
 
     def get_data_struct(self, pred_idx=0):
+        if self.stream_metrics:
+            return self._stream_data_struct(pred_idx)
         self.data_struct[pred_idx].finalize_tensors()
         returned = copy.deepcopy(self.data_struct[pred_idx])
         for key in ('rec.rec_tags', 'rec.tgt_tags', 'rec.outlier_users', 'rec.topk'):

@@ -11,7 +11,7 @@ class Evaluator(object):
         self.shared_metrics = [m.lower() for m in (config['shared_metrics'] or [])]
         unknown = [m for m in self.metrics + self.shared_metrics if m not in metrics_dict]
         if unknown:
-            raise NotImplementedError(f"metrics {unknown} are outside the hot path (Recall / NDCG / Entropy are built)")
+            raise NotImplementedError(f"metrics {unknown} are not built (built: {sorted(metrics_dict)})")
         self.metric_class = {m: metrics_dict[m](config) for m in self.metrics + self.shared_metrics}
 
     def evaluate(self, dataobject, pred_len=1):

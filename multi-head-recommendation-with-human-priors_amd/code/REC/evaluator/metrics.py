@@ -1,12 +1,17 @@
 """Ranking metrics over the [users, K+1] hit matrix (reference `code/REC/evaluator/metrics.py:17-41, 145-238`,
-`base_metric.py:37-81`).  Host-side numpy: per-user curves @1..K are summed over the rank's users; the trainer
-divides by the global user count after the all-reduce (reference trainer.py:1109-1123)."""
+`base_metric.py:37-81`; Hit / MRR / MAP / Precision: `metrics.py:44-142, 241-263`).  Host-side numpy: per-user curves @1..K are
+summed over the rank's users; the trainer divides by the global user count after the all-reduce (reference
+trainer.py:1109-1123).  With `stream_metrics` the collector hands out the sums themselves (`'rec.metric_sums'`,
+`'rec.entropy_sums'`: the device reduced them batch by batch) and the classes only name them."""
 import numpy as np
+
+COLUMNS = ('recall', 'ndcg', 'hit', 'mrr', 'map', 'precision')      # column order of 'rec.metric_sums' (mhr_eval_metric_sums)
 
 
 class _TopkMetric:
     name = ''
     needs = ('rec.topk',)
+    by_group = False                      # per-category / outlier breakdown (the reference has it for Recall and NDCG only)
 
     def __init__(self, config):
         self.topk = config['topk']
@@ -33,9 +38,31 @@ class _TopkMetric:
             out[key] = s[k - 1] if num_samples is None else (s[k - 1], num_samples)
         return out
 
+    def _from_sums(self, ms, pred_len):
+        """The streamed form: sums [G, 6, n_topk] / counts [G] with group 0 = every user, 1 + c = category c, last = outliers."""
+        sums, counts = ms['sums'][:, COLUMNS.index(self.name)], ms['counts']
+
+        def pack(g, prefix=None):
+            out = {}
+            for t, k in enumerate(self.topk):
+                key = f'{self.name}@{k}' if prefix is None else f'{prefix}-{self.name}@{k}'
+                out[key] = sums[g, t] if prefix is None else (sums[g, t], int(counts[g]))
+            return out
+        out = pack(0)
+        if self.by_group and self.num_prior_categories > 1 and self.eval_by_cat and ms['cats']:
+            for c in range(self.num_prior_categories):
+                out.update(pack(1 + c, self.int_to_category[c]))
+        if self.by_group and self.outlier_user_metrics is not None and pred_len == self.eval_pred_len - 1 and ms['outlier']:
+            out.update(pack(len(counts) - 1, f'outlier_{self.outlier_user_metrics}'))
+        return out
+
     def calculate_metric(self, dataobject, pred_len=1):
+        if 'rec.metric_sums' in dataobject:
+            return self._from_sums(dataobject.get('rec.metric_sums'), pred_len)
         hits, pos_len = self.used_info(dataobject)
         out = self._pack(self.curve(hits, pos_len))
+        if not self.by_group:
+            return out
         if self.num_prior_categories > 1 and self.eval_by_cat and 'rec.tgt_tags' in dataobject:
             tgt = dataobject.get('rec.tgt_tags')
             tgt = tgt.numpy() if hasattr(tgt, 'numpy') else np.asarray(tgt)
@@ -51,6 +78,7 @@ class _TopkMetric:
 
 class Recall(_TopkMetric):
     name = 'recall'
+    by_group = True
 
     def curve(self, hits, pos_len):
         return np.cumsum(hits, axis=1) / pos_len.reshape(-1, 1)
@@ -58,12 +86,47 @@ class Recall(_TopkMetric):
 
 class NDCG(_TopkMetric):
     name = 'ndcg'
+    by_group = True
 
     def curve(self, hits, pos_len):
         K = hits.shape[1]
         disc = 1.0 / np.log2(np.arange(2, K + 2, dtype=np.float64))
         ideal = np.cumsum(disc)[np.minimum(np.arange(K)[None, :], np.minimum(pos_len, K)[:, None] - 1)]
         return np.cumsum(np.where(hits, disc[None, :], 0.0), axis=1) / ideal
+
+
+class Hit(_TopkMetric):
+    name = 'hit'
+
+    def curve(self, hits, pos_len):
+        return (np.cumsum(hits, axis=1) > 0).astype(int)
+
+
+class MRR(_TopkMetric):
+    name = 'mrr'
+
+    def curve(self, hits, pos_len):
+        first = hits.argmax(axis=1)                                  # rank of the first hit (0 when there is none)
+        rr = np.where(hits.any(axis=1), 1.0 / (first + 1), 0.0)
+        return np.where(np.arange(hits.shape[1])[None, :] >= first[:, None], rr[:, None], 0.0)
+
+
+class MAP(_TopkMetric):
+    name = 'map'
+
+    def curve(self, hits, pos_len):
+        K = hits.shape[1]
+        ranks = np.arange(1, K + 1)
+        pre = hits.cumsum(axis=1) / ranks
+        sum_pre = np.cumsum(pre * hits.astype(np.float64), axis=1)
+        return sum_pre / np.minimum(ranks[None, :], np.minimum(pos_len, K)[:, None])
+
+
+class Precision(_TopkMetric):
+    name = 'precision'
+
+    def curve(self, hits, pos_len):
+        return hits.cumsum(axis=1) / np.arange(1, hits.shape[1] + 1)
 
 
 class Entropy:
@@ -75,6 +138,8 @@ class Entropy:
         self.topk = config['topk']
 
     def calculate_metric(self, dataobject, pred_len=1):
+        if 'rec.entropy_sums' in dataobject:
+            return {f'Entropy@{k}': v for k, v in zip(self.topk, dataobject.get('rec.entropy_sums'))}
         tags = dataobject.get('rec.rec_tags')
         tags = tags.numpy() if hasattr(tags, 'numpy') else np.asarray(tags)
         counts = np.cumsum(tags.astype(np.float64), axis=1)
@@ -88,4 +153,4 @@ class Entropy:
         return out
 
 
-metrics_dict = {'recall': Recall, 'ndcg': NDCG, 'entropy': Entropy}
+metrics_dict = {'recall': Recall, 'ndcg': NDCG, 'hit': Hit, 'mrr': MRR, 'map': MAP, 'precision': Precision, 'entropy': Entropy}

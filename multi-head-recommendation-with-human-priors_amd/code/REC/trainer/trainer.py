@@ -630,7 +630,7 @@ class Trainer(object):
         # metric sums -> one packed all-reduce (the reference reduces key by key, trainer.py:1109-1123)
         results = OrderedDict()
         struct = self.eval_collector.get_data_struct(-1)
-        results['shared'] = self.evaluator.evaluate(struct, pred_len=-1) if 'rec.rec_tags' in struct else OrderedDict()
+        results['shared'] = self.evaluator.evaluate(struct, pred_len=-1) if 'rec.rec_tags' in struct or 'rec.entropy_sums' in struct else OrderedDict()
         self.eval_collector.reset_all_tags()
         for p in self.metrics_pred_len_list:
             results[f"pred_{p}"] = self.evaluator.evaluate(self.eval_collector.get_data_struct(p), pred_len=p)

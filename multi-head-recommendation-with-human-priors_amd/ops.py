@@ -1861,3 +1861,70 @@ def hit_matrix(topk_idx, positives, n_pos):
     lib.call("mhr_hit_matrix", topk_idx.data_ptr(), B, k, positives.data_ptr(), positives.stride(0), n_pos, hit.data_ptr(),
              _stream())
     return hit
+
+
+# ------------------------------------------------------------------------------------------------
+# streaming evaluation metrics
+# ------------------------------------------------------------------------------------------------
+METRIC_COLUMNS = ("recall", "ndcg", "hit", "mrr", "map", "precision")     # the column order of mhr_eval_metric_sums
+METRIC_LIMITS = dict(K=2048, n_pred=16, n_topk=16, n_groups=32, n_tags=32)
+_METRIC_CACHE = {}
+
+
+def eval_metric_sums_workspace_bytes(B, n_pred, n_groups, n_topk):
+    n = lib.load().mhr_eval_metric_sums_workspace_bytes(int(B), int(n_pred), int(n_groups), int(n_topk))
+    if n < 0:
+        raise ValueError(f"eval_metric_sums: sizes outside the kernel's limits {METRIC_LIMITS} "
+                         f"(B={B}, n_pred={n_pred}, n_groups={n_groups}, n_topk={n_topk})")
+    return n
+
+
+def _metric_cached(key, make):
+    v = _METRIC_CACHE.get(key)
+    if v is None:
+        if len(_METRIC_CACHE) >= 64:
+            _METRIC_CACHE.clear()
+        v = _METRIC_CACHE[key] = make()
+    return v
+
+
+def eval_metric_sums(topk_idx, positives, pos_len, pred, topk, group_bits, n_groups, sums, counts, item_tag_bits=None,
+                     n_tags=0, entropy=None):
+    """One launch pair per batch: sums [n_pred, n_groups, 6, n_topk] f64 (columns METRIC_COLUMNS), counts [n_pred, n_groups] i64
+    and entropy [n_topk] f64 (with item_tag_bits [N] int32 words, bit c = tag c) get the batch's users ADDED - the caller owns
+    and zeroes the accumulators.  topk_idx [B, K] i64, positives [B, >= max(pred) + 1] i64, pos_len [B, >= max(pred) + 1] i32,
+    group_bits [B, n_pred] i32 words; pred / topk: host lists.  The discount tables and the workspace are cached per shape."""
+    import ctypes
+    _chk(topk_idx, "topk_idx", torch.int64)
+    _chk(pos_len, "pos_len", torch.int32)
+    _chk(group_bits, "group_bits", torch.int32)
+    _chk(sums, "sums", torch.float64)
+    _chk(counts, "counts", torch.int64)
+    if positives.dtype != torch.int64 or positives.stride(1) != 1 or not positives.is_cuda:
+        raise TypeError("positives: expected int64 rows on the GPU")
+    B, K = topk_idx.shape
+    n_pred, n_topk = len(pred), len(topk)
+    dev = topk_idx.device
+    assert tuple(group_bits.shape) == (B, n_pred) and positives.shape[0] == B and pos_len.shape[0] == B
+    assert min(positives.shape[1], pos_len.shape[1]) > max(pred), "eval_metric_sums: positives / pos_len hold fewer than max(pred) + 1 columns"
+    assert sums.numel() == n_pred * n_groups * len(METRIC_COLUMNS) * n_topk and counts.numel() == n_pred * n_groups
+    if (item_tag_bits is None) != (entropy is None):
+        raise ValueError("eval_metric_sums: item_tag_bits and entropy are given together or not at all")
+    if entropy is not None:
+        _chk(item_tag_bits, "item_tag_bits", torch.int32)
+        _chk(entropy, "entropy", torch.float64)
+        assert entropy.numel() == n_topk
+    nbytes = eval_metric_sums_workspace_bytes(B, n_pred, n_groups, n_topk)
+
+    def tables():
+        d = 1.0 / torch.log2(torch.arange(2, K + 2, dtype=torch.float64))
+        return torch.stack((d, torch.cumsum(d, 0))).to(dev)
+    disc = _metric_cached(("disc", dev, K), tables)
+    ws = _metric_cached(("ws", dev, nbytes), lambda: torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev))
+    pred_c, topk_c = _metric_cached(("lists", tuple(pred), tuple(topk)),
+                                    lambda: ((ctypes.c_int32 * n_pred)(*pred), (ctypes.c_int32 * n_topk)(*topk)))
+    _timed_call("mhr_eval_metric_sums", topk_idx.data_ptr(), B, K, positives.data_ptr(), positives.stride(0), pos_len.data_ptr(),
+                pos_len.stride(0), ctypes.addressof(pred_c), n_pred, ctypes.addressof(topk_c), n_topk, disc[0].data_ptr(),
+                disc[1].data_ptr(), group_bits.data_ptr(), int(n_groups), _ptr(item_tag_bits),
+                0 if item_tag_bits is None else item_tag_bits.numel(), int(n_tags), sums.data_ptr(), counts.data_ptr(),
+                _ptr(entropy), ws.data_ptr(), _stream())
