@@ -916,6 +916,38 @@ int mhr_eval_metric_sums(const int64_t* topk_idx, int B, int K, const int64_t* p
                          const uint32_t* group_bits, int n_groups, const uint32_t* item_tag_bits, int64_t n_items,
                          int n_tags, double* sums, int64_t* counts, double* entropy, void* workspace, void* stream);
 
+/* Catalog exposure (evaluator/metrics.py: ItemCoverage 473-516, AveragePopularity 519-585, ShannonEntropy 588-640, GiniIndex
+ * 643-696, TailPercentage 699-780) from an integer item histogram on the device instead of the reference's [users, max(topk)]
+ * item matrix.  With c_t[i] = occurrences of item i in the first cuts[t] columns of every accumulated list:
+ *   mhr_exposure_accumulate: one thread per (user b, rank j) of topk_idx [B, K] i64.  Rank j belongs to band t = the first cut
+ *     with j < cuts[t] (cuts: HOST array, strictly ascending, cuts[0] >= 1, cuts[n_cuts - 1] <= K; ranks at or beyond the last cut
+ *     are ignored) and adds 1 to band_counts[t][id] (band_counts [n_cuts, n_items] i32, +=, the caller owns and zeroes it), so
+ *     c_t[i] = sum_{s <= t} band_counts[s][i].  An id outside [0, n_items) writes nothing and adds 1 to bad[0] (sticky; the
+ *     caller reads it once, after the finalize).  Integer atomics only: the histogram does not depend on the batch split or
+ *     the launch order.
+ *   mhr_exposure_finalize: per cut t, with U = max_count users, phi = item_pop [n_items] i64 (NULL: zeros) and
+ *     tail = item_tail [n_items] u8 (NULL: zeros):
+ *       out_int [n_cuts, 4] i64 = (R = |{i : c_t[i] > 0}|,  sum_i c_t[i] phi[i],  sum_i c_t[i] (tail[i] != 0),  G)
+ *       out_f64 [n_cuts]   f64 = S = sum_{c_t[i] > 0} c_t[i] ln c_t[i]
+ *     G = sum (2 idx - N - 1) sorted_count over the R non-zero counts in non-decreasing order at idx = N - R + 1 .. N (N = n_items)
+ *       = sum_c c m_c (N - 2R + 2 s_c + m_c) over the count-of-counts m_c (s_c = items of non-zero count below c): exact.
+ *     A count above max_count is left out of G and adds 1 to bad[0] (a list held an item twice, or max_count is not the number
+ *     of accumulated users).  Both entries overwrite their outputs; band_counts is read only.
+ *     Two stages: 1024 items per workgroup are reduced in a fixed order to one partial per (workgroup, cut, value) and counted
+ *     into the count-of-counts table with integer atomics (counts below 64 through a per-workgroup table in LDS); one workgroup
+ *     per cut adds the partials in workgroup order and scans the table.  No floating-point atomics: S is summed in an order the item ids fix, the same histogram gives the same bits.
+ *   mhr_exposure_finalize_workspace_bytes: HOST size query, no launch:
+ *     ceil(n_items / 1024) * n_cuts * 4 * 8 + round_up_8(n_cuts * (max_count + 1) * 4) bytes; -1 outside the limits.
+ * Limits (checked on the host before any launch): 1 <= n_cuts <= 16; 1 <= n_items < 2^31; users per evaluation (max_count) < 2^31;
+ * 2 * n_items * max_count * k_max < 2^63 with k_max = the largest cut (the Gini numerator and the scan's intermediate products);
+ * the caller keeps sum_i c[i] phi[i] <= U * sum(phi) below 2^63. */
+int mhr_exposure_accumulate(const int64_t* topk_idx, int B, int K, const int32_t* cuts, int n_cuts, int64_t n_items,
+                            int32_t* band_counts, int32_t* bad, void* stream);
+int64_t mhr_exposure_finalize_workspace_bytes(int n_cuts, int64_t n_items, int64_t max_count);
+int mhr_exposure_finalize(const int32_t* band_counts, int n_cuts, int64_t n_items, const int64_t* item_pop,
+                          const uint8_t* item_tail, int64_t max_count, int k_max, int64_t* out_int, double* out_f64,
+                          int32_t* bad, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

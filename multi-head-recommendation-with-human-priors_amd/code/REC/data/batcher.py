@@ -100,6 +100,16 @@ class SeqStore:
         self.item_weights_by_cat = None if item_weights_by_cat is None else [torch.as_tensor(w, dtype=torch.float64).to(device)
                                                                              for w in item_weights_by_cat]
 
+    def item_train_counts(self):
+        """[item_num] int64: how often each item occurs in the users' training prefixes `user_seq[u][:train_seq_len[u]]`
+        (uid 0 is the padding user and the pad id 0 counts as 0) - the phi of AveragePopularity / TailPercentage."""
+        owner = torch.repeat_interleave(torch.arange(self.user_num, device=self.device), self.lens)
+        pos = torch.arange(self.items.numel(), device=self.device) - self.ptr[owner]
+        train = (pos < self.train_len[owner]) & (owner > 0)
+        counts = torch.bincount(self.items[train], minlength=self.item_num)
+        counts[0] = 0
+        return counts
+
     def sample_locations(self, max_len, pred_len, sample_last_only=False):
         """[n, 2] (uid, context_end) exactly as dataload.py:163-195."""
         out = []
@@ -323,6 +333,14 @@ class SeqEvalBatcher:
         if self.packed_rows:
             n_hist = store.train_len if phase == 'valid' else store.lens - self.E
             self.ctx_len_host = n_hist[self.users].clamp(0, self.L).cpu()
+
+    @property
+    def item_counts(self):
+        """[item_num] int64 training interactions per item, next to `item_tags` (counted on first use: only the exposure metrics
+        read it)."""
+        if self.__dict__.get('_item_counts') is None:
+            self._item_counts = self.store.item_train_counts()
+        return self._item_counts
 
     def __len__(self):
         return math.ceil(self.users.numel() / self.B)

@@ -8,13 +8,18 @@ everything stays on the device until the per-pred_len `[B, K+1]` result is appen
 `stream_metrics: True` (default off) stores nothing per batch: one `eval_metric_sums` launch adds the batch's users onto a small
 fp64 accumulator on the device (the summed metric curves at `topk`, over all users and per category / outlier group), and
 `get_data_struct` hands the sums out as `'rec.metric_sums'` / `'rec.entropy_sums'` after one device->host copy.
+
+A catalog-exposure metric in `shared_metrics` (ItemCoverage, AveragePopularity, ShannonEntropy, GiniIndex, TailPercentage), with
+`stream_metrics` on or off, adds every batch's merged lists to an integer item histogram on the device (`exposure_accumulate`);
+`get_data_struct(-1)` reduces it to a few integers per cut-off (`exposure_finalize`) and hands them out as
+`'rec.exposure_sums'`.  The lists are the merged ones the accuracy metrics see, not the reference's per-head `rec.items`.
 """
 import copy
 
 import numpy as np
 import torch
 
-from .metrics import COLUMNS
+from .metrics import COLUMNS, EXPOSURE_METRICS, tail_items
 
 
 class DataStruct(object):
@@ -75,6 +80,9 @@ class Collector(object):
         self.stream_metrics = bool(config.get('stream_metrics', False))
         if self.stream_metrics:
             self._stream_init(config)
+        self.exposure = [m.lower() for m in (config.get('shared_metrics') or []) if m.lower() in EXPOSURE_METRICS]
+        if self.exposure:
+            self._exposure_init(config)
 
     def set_all_tags(self, item_tags):
         self.all_tags = item_tags
@@ -198,6 +206,95 @@ class Collector(object):
         counts[i].zero_()
         return out
 
+    # ---- catalog exposure: an integer item histogram instead of the reference's [users, max(topk)] item matrix ---------------
+    def _exposure_init(self, config):
+        from mhr_amd.ops import EXPOSURE_LIMITS
+        self._ex_cuts = sorted(set(int(k) for k in self.topk))
+        if len(self._ex_cuts) > EXPOSURE_LIMITS['n_cuts']:
+            raise ValueError(f"exposure metrics: {len(self._ex_cuts)} distinct cut-offs exceed the kernel's limit of "
+                             f"{EXPOSURE_LIMITS['n_cuts']}")
+        self._ex_needs_counts = any(EXPOSURE_METRICS[m].needs_item_counts for m in self.exposure)
+        self._ex_tail_ratio = config.get('tail_ratio')
+        self._ex_item_num = config.get('item_num')
+        self._ex_pop = self._ex_tail = None          # [N] int64 training counts / [N] uint8 long-tail mask (set_item_counts)
+        self._ex_hist = None                         # device int32 [n_cuts, N]: occurrences per rank band and item
+        self._ex_out = None                          # device int64 words: ints [n_cuts, 4] | S [n_cuts] (f64 bits) | bad (int32)
+        self._ex_users = 0
+
+    def set_item_counts(self, counts):
+        """counts [N] int64: training interactions per item (phi; `SeqStore.item_train_counts`).  AveragePopularity and
+        TailPercentage need it; the long-tail set (config `tail_ratio`) is built here, once."""
+        if not self.exposure:
+            return
+        counts = torch.as_tensor(counts)
+        if counts.dim() != 1 or counts.dtype != torch.int64:
+            raise ValueError("set_item_counts: expected an int64 [item_num] tensor")
+        if bool((counts < 0).any()):
+            raise ValueError("set_item_counts: negative interaction counts")
+        if self._ex_hist is not None and counts.numel() != self._ex_hist.shape[1]:
+            raise ValueError(f"set_item_counts: {counts.numel()} items, the running histogram holds {self._ex_hist.shape[1]}")
+        self._ex_pop, self._ex_tail = counts.contiguous(), tail_items(counts, self._ex_tail_ratio)
+
+    def _exposure_check_counts(self):
+        if self._ex_needs_counts and self._ex_pop is None:
+            raise ValueError("AveragePopularity / TailPercentage need the items' training interaction counts: call "
+                             "Collector.set_item_counts(SeqStore.item_train_counts()) before the evaluation")
+
+    def _exposure_views(self, buf):
+        T = len(self._ex_cuts)
+        return buf[:4 * T].view(T, 4), buf[4 * T:5 * T].view(torch.float64), buf[5 * T:].view(torch.int32)[:1]
+
+    def _exposure_collect(self, topk_idx):
+        from mhr_amd import ops
+        dev = topk_idx.device
+        if self._ex_hist is None or self._ex_hist.device != dev:
+            if self._ex_users:
+                raise RuntimeError("exposure metrics: the evaluation changed its device between batches")
+            N = self._ex_pop.numel() if self._ex_pop is not None else (
+                self.all_tags.shape[0] if self.all_tags is not None else self._ex_item_num)
+            if N is None:
+                raise ValueError("exposure metrics: the catalog size is unknown (set_item_counts, set_all_tags or config['item_num'])")
+            self._ex_hist = torch.zeros(len(self._ex_cuts), int(N), dtype=torch.int32, device=dev)
+            self._ex_out = torch.zeros(5 * len(self._ex_cuts) + 1, dtype=torch.int64, device=dev)
+        ops.exposure_accumulate(topk_idx.contiguous(), self._ex_cuts, self._ex_hist.shape[1], self._ex_hist,
+                                self._exposure_views(self._ex_out)[2])
+        self._ex_users += topk_idx.shape[0]
+
+    def _exposure_hand_out(self, struct):
+        """All-reduce the histogram and the user count, finalize, one small device->host copy, zero - as the streamed sums are
+        handed out and zeroed."""
+        if self._ex_hist is None:
+            return
+        from mhr_amd import distributed as D, ops
+        T, N = self._ex_hist.shape
+        ints, S, bad = self._exposure_views(self._ex_out)
+        users = D.allreduce_exposure(self._ex_hist, self._ex_users, bad)
+        if users == 0:
+            return
+        lim = ops.EXPOSURE_LIMITS['users']
+        if users > lim or 2 * N * users * self._ex_cuts[-1] >= 2 ** 63:
+            raise ValueError(f"exposure metrics: {users} users x {N} items x k = {self._ex_cuts[-1]} exceed the kernel's limits "
+                             f"(users <= {lim}, 2 * items * users * k < 2^63)")
+        dev = self._ex_hist.device
+        pop = tail = None
+        if self._ex_pop is not None:
+            if self._ex_pop.numel() != N:
+                raise ValueError(f"set_item_counts gave {self._ex_pop.numel()} items, the histogram holds {N}")
+            if users * int(self._ex_pop.sum()) >= 2 ** 63:
+                raise ValueError("exposure metrics: users x training interactions does not fit 63 bits")
+            self._ex_pop, self._ex_tail = self._ex_pop.to(dev), self._ex_tail.to(dev)
+            pop, tail = self._ex_pop, self._ex_tail
+        ops.exposure_finalize(self._ex_hist, T, N, users, self._ex_cuts[-1], ints, S, bad, item_pop=pop, item_tail=tail)
+        host = self._ex_out.cpu()                                          # the one device->host copy
+        self._ex_hist.zero_()
+        self._ex_out.zero_()
+        self._ex_users = 0
+        ints, S, bad = self._exposure_views(host)
+        if int(bad[0]):
+            raise RuntimeError(f"exposure metrics: {int(bad[0])} recommended ids outside [0, {N}) or items counted more often "
+                               "than there are users (a list holding an item twice)")
+        struct.set('rec.exposure_sums', dict(ints=ints.numpy().copy(), S=S.numpy().copy(), N=N, U=users, cuts=list(self._ex_cuts)))
+
     # ------------------------------------------------------------------------------------------
     def _decode(self, scores, top_k, detail):
         """-> merged item ids [B, top_k] int64 on the device."""
@@ -239,6 +336,8 @@ class Collector(object):
                            log_detailed_results=False):
         from mhr_amd import ops
         stored = not self.stream_metrics
+        if self.exposure:
+            self._exposure_check_counts()
         if stored and tag_category is not None:
             for p in self.metrics_pred_len_list:
                 self.data_struct[p].update_tensor('rec.tgt_tags', torch.any(tag_category[:, :p + 1].bool(), dim=1))
@@ -250,6 +349,8 @@ class Collector(object):
         dev = topk_idx.device
         positive_i = positive_i.to(dev).contiguous()
         B = topk_idx.shape[0]
+        if self.exposure:
+            self._exposure_collect(topk_idx)
         if stored and self.all_tags is not None:
             self.data_struct[-1].update_tensor('rec.rec_tags', self.all_tags.to(dev)[topk_idx])
         # distinct positives among the ascending-sorted targets (reference collector.py:301-304)
@@ -271,6 +372,12 @@ class Collector(object):
         return {}
 
     def get_data_struct(self, pred_idx=0):
+        returned = self._collected_struct(pred_idx)
+        if self.exposure and pred_idx == -1:
+            self._exposure_hand_out(returned)
+        return returned
+
+    def _collected_struct(self, pred_idx):
         if self.stream_metrics:
             return self._stream_data_struct(pred_idx)
         self.data_struct[pred_idx].finalize_tensors()

@@ -2,7 +2,9 @@
 `base_metric.py:37-81`; Hit / MRR / MAP / Precision: `metrics.py:44-142, 241-263`).  Host-side numpy: per-user curves @1..K are
 summed over the rank's users; the trainer divides by the global user count after the all-reduce (reference
 trainer.py:1109-1123).  With `stream_metrics` the collector hands out the sums themselves (`'rec.metric_sums'`,
-`'rec.entropy_sums'`: the device reduced them batch by batch) and the classes only name them."""
+`'rec.entropy_sums'`: the device reduced them batch by batch) and the classes only name them.
+The catalog-exposure metrics (reference `metrics.py:473-780`) are final values formed from the integer sums of the device's item
+histogram (`'rec.exposure_sums'`); they belong in `shared_metrics`."""
 import numpy as np
 
 COLUMNS = ('recall', 'ndcg', 'hit', 'mrr', 'map', 'precision')      # column order of 'rec.metric_sums' (mhr_eval_metric_sums)
@@ -153,4 +155,93 @@ class Entropy:
         return out
 
 
-metrics_dict = {'recall': Recall, 'ndcg': NDCG, 'hit': Hit, 'mrr': MRR, 'map': MAP, 'precision': Precision, 'entropy': Entropy}
+class _ExposureMetric:
+    """Catalog-level metrics of the merged recommendation lists (reference metrics.py:473-780), from the integer sums the device
+    forms out of its item histogram (`'rec.exposure_sums'`, mhr_exposure_finalize): ints [n_cuts, 4] = (R, sum c*phi,
+    sum c*tail, G) and S [n_cuts] = sum c ln c per ascending cut-off in `cuts`, N items, U users.  With T = U*k occurrences the
+    values are final (not sums over users) and do not depend on pred_len: shared metrics."""
+    name = ''
+    needs = ('rec.exposure_sums',)
+    needs_item_counts = False
+
+    def __init__(self, config):
+        self.topk = config['topk']
+
+    def value(self, R, P, Tl, G, S, N, T):
+        raise NotImplementedError
+
+    def calculate_metric(self, dataobject, pred_len=-1):
+        ex = dataobject.get('rec.exposure_sums')
+        ints, S = np.asarray(ex['ints'], dtype=np.int64), np.asarray(ex['S'], dtype=np.float64)
+        N, U, cuts = int(ex['N']), int(ex['U']), [int(c) for c in ex['cuts']]
+        out = {}
+        for k in self.topk:
+            t = cuts.index(k)
+            R, P, Tl, G = (int(v) for v in ints[t])
+            out[f'{self.name}@{k}'] = float(self.value(R, P, Tl, G, np.float64(S[t]), N, U * k)) if U > 0 else 0.0
+        return out
+
+
+class ItemCoverage(_ExposureMetric):
+    name = 'itemcoverage'
+
+    def value(self, R, P, Tl, G, S, N, T):
+        return np.float64(R) / np.float64(N)                                 # metrics.py:515-516
+
+
+class AveragePopularity(_ExposureMetric):
+    name = 'averagepopularity'
+    needs_item_counts = True
+
+    def value(self, R, P, Tl, G, S, N, T):
+        return np.float64(P) / np.float64(T)                                 # metrics.py:568, 581: every user divides by the same k
+
+
+class TailPercentage(_ExposureMetric):
+    name = 'tailpercentage'
+    needs_item_counts = True
+
+    def value(self, R, P, Tl, G, S, N, T):
+        return np.float64(Tl) / np.float64(T)                                # metrics.py:764, 777
+
+
+class ShannonEntropy(_ExposureMetric):
+    name = 'shannonentropy'
+
+    def value(self, R, P, Tl, G, S, N, T):
+        # metrics.py:634-640: sum -p ln p with p = c / T is ln T - S / T; the reference divides by the items recommended
+        return max(np.log(np.float64(T)) - S / np.float64(T), np.float64(0.0)) / np.float64(R)
+
+
+class GiniIndex(_ExposureMetric):
+    name = 'giniindex'
+
+    def value(self, R, P, Tl, G, S, N, T):
+        return np.float64(G) / np.float64(T) / np.float64(N)                 # metrics.py:694-695
+
+
+def tail_items(counts, tail_ratio):
+    """The reference's long-tail set (TailPercentage.get_tail, metrics.py:743-749) as a uint8 mask [N]: the counter holds the
+    items i >= 1 with counts[i] > 0; tail_ratio > 1 keeps those with counts <= tail_ratio, otherwise the first
+    max(int(len(counter) * tail_ratio), 1) of the counter ordered by (count, id).  None or <= 0 reads as 0.1 (metrics.py:724)."""
+    import torch
+    counts = torch.as_tensor(counts).long()
+    if tail_ratio is None or tail_ratio <= 0:
+        tail_ratio = 0.1
+    seen = counts > 0
+    seen[0] = False
+    mask = torch.zeros_like(counts, dtype=torch.uint8)
+    if tail_ratio > 1:
+        mask[seen & (counts <= tail_ratio)] = 1
+        return mask
+    ids = torch.nonzero(seen).flatten()                                      # ascending ids: a stable sort by count orders (count, id)
+    if ids.numel():
+        order = torch.sort(counts[ids], stable=True)[1]
+        mask[ids[order[:max(int(ids.numel() * tail_ratio), 1)]]] = 1
+    return mask
+
+
+EXPOSURE_METRICS = {'itemcoverage': ItemCoverage, 'averagepopularity': AveragePopularity, 'shannonentropy': ShannonEntropy,
+                    'giniindex': GiniIndex, 'tailpercentage': TailPercentage}
+metrics_dict = {'recall': Recall, 'ndcg': NDCG, 'hit': Hit, 'mrr': MRR, 'map': MAP, 'precision': Precision, 'entropy': Entropy,
+                **EXPOSURE_METRICS}

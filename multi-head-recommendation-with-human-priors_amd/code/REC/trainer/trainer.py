@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from REC.evaluator import Collector, Evaluator
+from REC.evaluator.metrics import EXPOSURE_METRICS
 from REC.utils import early_stopping
 from REC.utils.lr_scheduler import cosine_warmup_factor
 
@@ -619,6 +620,8 @@ class Trainer(object):
         if item_tags is None:
             item_tags = eval_data.item_tags
         self.compute_item_feature(item_tags)
+        if self.eval_collector.exposure and getattr(eval_data, "item_counts", None) is not None:
+            self.eval_collector.set_item_counts(eval_data.item_counts)       # phi of AveragePopularity / TailPercentage
         n_local = 0
         for batched in eval_data:
             fused, positive_u, positive_i, target_tags, outlier = self._full_sort_batch_eval(batched)
@@ -630,7 +633,11 @@ class Trainer(object):
         # metric sums -> one packed all-reduce (the reference reduces key by key, trainer.py:1109-1123)
         results = OrderedDict()
         struct = self.eval_collector.get_data_struct(-1)
-        results['shared'] = self.evaluator.evaluate(struct, pred_len=-1) if 'rec.rec_tags' in struct or 'rec.entropy_sums' in struct else OrderedDict()
+        shared = 'rec.rec_tags' in struct or 'rec.entropy_sums' in struct or 'rec.exposure_sums' in struct
+        results['shared'] = self.evaluator.evaluate(struct, pred_len=-1) if shared else OrderedDict()
+        # the exposure metrics are final values of the global histogram (all-reduced before its finalize), not per-rank sums over
+        # users: they bypass the packed all-reduce and its division
+        final = OrderedDict((k, results['shared'].pop(k)) for k in list(results['shared']) if k.split('@')[0] in EXPOSURE_METRICS)
         self.eval_collector.reset_all_tags()
         for p in self.metrics_pred_len_list:
             results[f"pred_{p}"] = self.evaluator.evaluate(self.eval_collector.get_data_struct(p), pred_len=p)
@@ -656,6 +663,8 @@ class Trainer(object):
             else:
                 summary[name][k] = round(vec[i] / max(1, total), dp)
                 i += 1
+        for k, v in final.items():
+            summary['shared'][k] = round(float(v), dp)
         self._check_pack_guard()
         self.model.train()
         return summary

@@ -203,3 +203,17 @@ def allreduce_metric_sums(values):
     if world_size() > 1:
         dist.all_reduce(values, op=dist.ReduceOp.SUM)
     return values
+
+
+def allreduce_exposure(band_counts, n_users, bad):
+    """The exposure histogram of an evaluation over all ranks: one integer SUM all-reduce of band_counts (int32, in place) and
+    one of (users, bad ids), issued before the finalize so every rank reduces the same global histogram and raises - or not -
+    together (`bad`: int32 [1] on the device, replaced by the global count).  -> the global user count.  Integer sums: the
+    result does not depend on the reduction order.  One rank: nothing is issued."""
+    if world_size() > 1:
+        n = torch.cat((torch.tensor([int(n_users)], dtype=torch.int64, device=band_counts.device), bad.long()))
+        dist.all_reduce(band_counts, op=dist.ReduceOp.SUM)
+        dist.all_reduce(n, op=dist.ReduceOp.SUM)
+        bad.copy_(n[1:].clamp(max=2 ** 31 - 1).int())
+        return int(n[0])
+    return int(n_users)

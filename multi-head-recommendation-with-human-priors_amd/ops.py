@@ -1928,3 +1928,66 @@ def eval_metric_sums(topk_idx, positives, pos_len, pred, topk, group_bits, n_gro
                 disc[1].data_ptr(), group_bits.data_ptr(), int(n_groups), _ptr(item_tag_bits),
                 0 if item_tag_bits is None else item_tag_bits.numel(), int(n_tags), sums.data_ptr(), counts.data_ptr(),
                 _ptr(entropy), ws.data_ptr(), _stream())
+
+
+# ------------------------------------------------------------------------------------------------
+# catalog exposure: item histogram -> coverage / popularity / tail / entropy / Gini sums
+# ------------------------------------------------------------------------------------------------
+EXPOSURE_COLUMNS = ("recommended", "popularity", "tail", "gini")          # the columns of mhr_exposure_finalize's out_int
+EXPOSURE_LIMITS = dict(n_cuts=16, n_items=2 ** 31 - 1, users=2 ** 31 - 1)
+
+
+def _exposure_cuts(cuts):
+    import ctypes
+    cuts = [int(c) for c in cuts]
+    return _metric_cached(("cuts", tuple(cuts)), lambda: (ctypes.c_int32 * max(len(cuts), 1))(*cuts))
+
+
+def exposure_accumulate(topk_idx, cuts, n_items, band_counts, bad):
+    """One launch per batch: every (user, rank < cuts[-1]) of topk_idx [B, K] i64 adds 1 to band_counts[t][id], t = the first cut
+    above the rank (cuts: ascending host list).  band_counts: int32, at least [len(cuts), n_items] words; bad: int32 [1], counts
+    the ids outside [0, n_items) (they write nothing).  The caller owns and zeroes both."""
+    import ctypes
+    _chk(topk_idx, "topk_idx", torch.int64)
+    _chk(band_counts, "band_counts", torch.int32)
+    _chk(bad, "bad", torch.int32)
+    if topk_idx.dim() != 2:
+        raise ValueError("exposure_accumulate: topk_idx must be [B, K]")
+    if band_counts.numel() < len(cuts) * int(n_items) or bad.numel() < 1:
+        raise ValueError(f"exposure_accumulate: band_counts holds {band_counts.numel()} words, "
+                         f"{len(cuts)} cuts x {n_items} items need {len(cuts) * int(n_items)}")
+    B, K = topk_idx.shape
+    _timed_call("mhr_exposure_accumulate", topk_idx.data_ptr(), B, K, ctypes.addressof(_exposure_cuts(cuts)), len(cuts),
+                int(n_items), band_counts.data_ptr(), bad.data_ptr(), _stream())
+
+
+def exposure_finalize_workspace_bytes(n_cuts, n_items, max_count):
+    n = lib.load().mhr_exposure_finalize_workspace_bytes(int(n_cuts), int(n_items), int(max_count))
+    if n < 0:
+        raise ValueError(f"exposure_finalize: sizes outside the kernel's limits {EXPOSURE_LIMITS} "
+                         f"(n_cuts={n_cuts}, n_items={n_items}, users={max_count})")
+    return n
+
+
+def exposure_finalize(band_counts, n_cuts, n_items, max_count, k_max, out_int, out_f64, bad, item_pop=None, item_tail=None):
+    """out_int [n_cuts, 4] i64 (columns EXPOSURE_COLUMNS) and out_f64 [n_cuts] f64 (sum c ln c) from the histogram of
+    `exposure_accumulate`; max_count = the users accumulated, k_max = the largest cut, item_pop [n_items] i64 / item_tail
+    [n_items] u8 optional.  Counts above max_count add to bad.  The workspace is cached per size."""
+    _chk(band_counts, "band_counts", torch.int32)
+    _chk(out_int, "out_int", torch.int64)
+    _chk(out_f64, "out_f64", torch.float64)
+    _chk(bad, "bad", torch.int32)
+    if band_counts.numel() < int(n_cuts) * int(n_items) or out_int.numel() < 4 * int(n_cuts) or out_f64.numel() < int(n_cuts):
+        raise ValueError("exposure_finalize: band_counts / out_int / out_f64 are smaller than n_cuts x n_items / n_cuts x 4 / n_cuts")
+    if item_pop is not None:
+        _chk(item_pop, "item_pop", torch.int64)
+    if item_tail is not None:
+        _chk(item_tail, "item_tail", torch.uint8)
+    for t, what in ((item_pop, "item_pop"), (item_tail, "item_tail")):
+        if t is not None and t.numel() != int(n_items):
+            raise ValueError(f"exposure_finalize: {what} holds {t.numel()} entries, n_items = {n_items}")
+    nbytes = exposure_finalize_workspace_bytes(n_cuts, n_items, max_count)
+    dev = band_counts.device
+    ws = _metric_cached(("ws", dev, nbytes), lambda: torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev))
+    _timed_call("mhr_exposure_finalize", band_counts.data_ptr(), int(n_cuts), int(n_items), _ptr(item_pop), _ptr(item_tail),
+                int(max_count), int(k_max), out_int.data_ptr(), out_f64.data_ptr(), bad.data_ptr(), ws.data_ptr(), _stream())
