@@ -408,7 +408,7 @@ int mhr_softmax_attn_bwd(const void* q, const void* k, const void* v, int64_t ro
 
 /* ------------------------------------------------------------------------------------------
  * Token compaction (replaces the boolean-mask indexing of model/IDNet/hstu.py:688-690, 814-829 and its host-side
- * `mask.sum() == 0` branch).  mask [n_groups, n_slots] uint8 (0/1) marks the live (group, slot) pairs; q_all
+ * `mask.sum() == 0` branch).  mask [n_groups, n_slots] uint8 (nonzero = live) marks the live (group, slot) pairs; q_all
  * [n_groups, n_slots], p_all / o_all [n_slots] int32 are static tables (query row, target row, prediction offset
  * of a slot).  For every group the live slots are written in ascending slot order:
  *   q_idx / p_idx / o_idx [n_groups, tok_cap][j] = table value of the j-th live slot,  n_tok[g] = min(#live, tok_cap)

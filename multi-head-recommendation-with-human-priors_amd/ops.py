@@ -834,7 +834,7 @@ def softmax_attn_bwd(qkv, out, d_out, lse, n_seqs, max_len, n_heads, n_kv_heads,
 # sampled softmax
 # ------------------------------------------------------------------------------------------------
 def token_compact(mask, q_all, p_all, o_all, tok_cap=None, slot_map=False, packed=None):
-    """Ordered compaction of live (group, slot) pairs.  mask [G, n_slots] bool/uint8; q_all [G, n_slots] int32;
+    """Ordered compaction of live (group, slot) pairs.  mask [G, n_slots] bool/uint8 (any nonzero byte is live); q_all [G, n_slots] int32;
     p_all, o_all [n_slots] int32.  Returns (q_idx, p_idx, o_idx [G, cap] int32 - entries beyond n_tok undefined -,
     n_tok [G] int32) with cap = tok_cap (default n_slots) rounded up to a multiple of 32.  No host sync.
     slot_map: also return tok_of_slot [G, n_slots] int32 (list position of a live slot, -1 otherwise).
