@@ -572,6 +572,9 @@ int mhr_nce_bwd_negs(const void* qn, const void* negs, const uint32_t* supp, int
  *   n_valid_tok = n_valid_row - #suppressed, rank_tok = rank_row - #suppressed with s_j > s_pos (rank_row must have been
  *   counted against this token's target: the caller gives the row kernel the target of the row's first token).
  *   Then mhr_nce_finalize on the token arrays as usual.
+ * mhr_nce_shared_fwd_rows: the same four outputs, bit for bit, from the row maps (row_first, n_row_dev of mhr_row_maps) instead of
+ *   tok2row: a half-wave per (group, row) loads the query row once and walks the row's tokens; the grid is sized by the device.
+ *   The product path's form; pn_rows and qn_row 16-byte aligned.
  * mhr_nce_shared_bwd_tokens: mhr_nce_bwd_tokens reading qn / u / q_inv of the token's ROW; takes the token's suppressed
  *   negatives out of u (bf16-rounded, as the row kernel accumulated them) and subtracts their share from d_negs
  *   ([n_groups, n_neg, dim] f32, may be NULL); writes lw_out per token.
@@ -593,6 +596,12 @@ int mhr_nce_shared_fwd_tokens(const void* pn_rows, int64_t n_p_rows, const int32
                               const float* logit_scale_dev, const uint32_t* fix_words,
                               const int32_t* fix_slot_of_row, const int32_t* fix_any,
                               float* s_pos, float* sum_tok, int32_t* n_valid_tok, int32_t* rank_tok, void* stream);
+int mhr_nce_shared_fwd_rows(const void* pn_rows, int64_t n_p_rows, const int32_t* p_idx, const int32_t* row_first,
+                            const int32_t* n_row_dev, int n_groups, int tok_cap, int row_cap, const void* qn_row,
+                            const float* sum_row, const int32_t* n_valid_row, const int32_t* rank_row,
+                            const void* negs, int n_neg, int dim, const float* logit_scale_dev,
+                            const uint32_t* fix_words, const int32_t* fix_slot_of_row, const int32_t* fix_any,
+                            float* s_pos, float* sum_tok, int32_t* n_valid_tok, int32_t* rank_tok, void* stream);
 int mhr_nce_shared_bwd_tokens(const void* qn_row, const float* u_row, const float* q_inv_row, int row_cap,
                               const int32_t* tok2row, const void* pn, int dim, int n_groups,
                               const int32_t* n_tok_dev, int tok_cap, const float* logit_scale_dev,
@@ -606,7 +615,9 @@ int mhr_nce_shared_bwd_tokens(const void* qn_row, const float* u_row, const floa
  * mhr_nce_shared_bwd_rows: a half-wave per (group, row): dq_rows[row_q[r]] += the row's gradient (chain rule once per row),
  *   lw_row[r] written, d(logit_scale) added, suppressed pairs taken out of u and of d_negs.  exclusive_rows != 0: the caller
  *   guarantees that no two (group, row) pairs name the same query row (the groups read disjoint decoding heads) - the add is
- *   then a plain read-modify-write; otherwise one float-atomic set per row.
+ *   then a plain read-modify-write; otherwise one float-atomic set per row.  exclusive_rows == 2: the caller guarantees in
+ *   addition that those rows of dq_rows hold zeros and that this launch alone writes them: the gradient is stored without the
+ *   read (the stored value is 0 + x, what the read-modify-write leaves, bit for bit).
  * mhr_nce_shared_bwd_targets: one wave per row of p_rows: dp_rows[m] += the gradient of every token of every group that
  *   points at it, gathered through tok_of_slot (plain read-modify-write, no atomics, bitwise reproducible). */
 int mhr_nce_shared_bwd_rows(const void* qn_row, const float* u_row, const float* q_inv_row, const int32_t* row_q,

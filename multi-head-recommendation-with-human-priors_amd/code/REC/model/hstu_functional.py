@@ -738,6 +738,8 @@ class NceLossFn(Function):
             bufs = (torch.zeros(q_shape, dtype=torch.float32, device=d_out.device),
                     torch.zeros(p_shape, dtype=torch.float32, device=d_out.device), None, None, None)
         dq, dp, d_negs0, d_ls0, lw_row = bufs
+        # dq: either the accumulator the early prep zeroed for this backward or the zeros made above; ops.nce_bwd below is its
+        # only writer before it is returned, so the row-wise kernel may store into it without reading the zeros back
         if not ctx.needs_input_grad[2]:
             d_negs0 = None
         if ctx.bucket_weight is not None:
@@ -747,7 +749,8 @@ class NceLossFn(Function):
             if sv.bucket_idx is not None:
                 w = w / sv.bucket_cnt.clamp_min(1.0)                      # d(mean)/d(loss_t) = 1 / count of the bucket
         d_negs, d_ls = ops.nce_bwd(sv, w, logit_scale.detach().view(1), q_idx, p_idx, dq, dp, d_negs=d_negs0, d_logit_scale=d_ls0,
-                                   want_negs=ctx.needs_input_grad[2], lw_row=lw_row, exclusive_q_rows=ctx.exclusive_q_rows)
+                                   want_negs=ctx.needs_input_grad[2], lw_row=lw_row, exclusive_q_rows=ctx.exclusive_q_rows,
+                                   dq_rows_zero=True)
         ctx.sv = None
         if d_negs is not None:
             d_negs = _deposit_f32_grad(sv.negs, d_negs)

@@ -184,6 +184,153 @@ __global__ __launch_bounds__(256) void shared_tok_fwd_kernel(
 }
 
 // ------------------------------------------------------------------------------------------
+// forward, per query ROW: what shared_tok_fwd_kernel writes, bit for bit, with the row's vector loaded once
+// ------------------------------------------------------------------------------------------
+// A HALF-wave per (group, row), as in shared_bwd_rows_kernel: the query row is loaded ONCE into registers (the per-token kernel
+// fetches it once per prediction offset), lane hl of a half = token hl of ITS row for the per-token scalars and the dependent
+// look-ups (target row -> table slot -> any-hit flag), and the target rows of up to FB tokens are requested before the first dot
+// product is taken.  The arithmetic per token is the per-token kernel's: 8 consecutive columns per lane, fp32 products summed in
+// column order, the same half-wave butterfly, the same whole-wave visit of a token's suppressed negatives.  The grid is sized by
+// the device (the launcher), each wave strides over the rows and asks for the next trip's row bounds and first target indices
+// before it consumes the current ones.  cfg1 step (kernel trace, 273.6 k tokens on 62.7 k rows): 42 us against the per-token
+// kernel's 57 us on the same box; 87 VGPRs, 5 waves per SIMD ("Token side of the row-sharing loss").
+__global__ __launch_bounds__(256) void shared_rows_fwd_kernel(
+    const bf16_t* __restrict__ pn_rows, int n_p_rows, const int32_t* __restrict__ p_idx, const int32_t* __restrict__ row_first,
+    const int32_t* __restrict__ n_row_dev, int tok_cap, int row_cap, const bf16_t* __restrict__ qn_row,
+    const float* __restrict__ sum_row, const int32_t* __restrict__ n_valid_row, const int32_t* __restrict__ rank_row,
+    const bf16_t* __restrict__ negs, int n_neg, int dim, const float* __restrict__ logit_scale_dev,
+    const uint32_t* __restrict__ fixw, int n_rows_pad, const int32_t* __restrict__ slot_of_row,
+    const int32_t* __restrict__ fix_any, float* __restrict__ s_pos,
+    float* __restrict__ sum_tok, int32_t* __restrict__ n_valid_tok, int32_t* __restrict__ rank_tok) {
+  const int n_tiles = (n_neg + 31) >> 5;
+  {
+    const int64_t grp = blockIdx.z, to = grp * tok_cap, ro = grp * row_cap;
+    p_idx += to; row_first += ro; n_row_dev += grp; s_pos += to; sum_tok += to;
+    qn_row += ro * dim; sum_row += ro;
+    if (n_valid_row) { n_valid_row += ro; n_valid_tok += to; }
+    if (rank_row) { rank_row += ro; rank_tok += to; }
+    negs += grp * (int64_t)((n_neg + 31) & ~31) * dim;
+    fixw += grp * (int64_t)n_tiles * n_rows_pad;
+    fix_any += grp * (int64_t)n_rows_pad;
+    if (slot_of_row) slot_of_row += grp * (int64_t)n_p_rows;
+  }
+  const int n_row = min(*n_row_dev, row_cap - 1);
+  const int lane = threadIdx.x & 63, hl = lane & 31, hw = lane >> 5;
+  const int wave_g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), n_waves = gridDim.x * (blockDim.x >> 6);
+  const float scale = clamp_scale(logit_scale_dev);
+  const float c1 = scale * LOG2E;
+  constexpr int FB = 8;                                              // target rows in flight per half
+  const int d0 = hl * 8;
+  const bool in_dim = d0 < dim;
+  const int d0w = lane * 4;                                          // (whole-wave layout of the hit path: 4 columns per lane)
+  const bool in_dim_w = d0w < dim;
+  auto half_sum = [](float v) {
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+  };
+  bf16x8 z;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) z[e] = (bf16_t)0.f;
+  // the next trip's row bounds and the target indices of its first 32 tokens
+  int nt0 = 0, nt1 = 0;
+  if (wave_g * 2 + hw < n_row) {
+    nt0 = row_first[wave_g * 2 + hw];
+    nt1 = min(row_first[wave_g * 2 + hw + 1], tok_cap);
+  }
+  int npi = nt0 + hl < nt1 ? p_idx[nt0 + hl] : 0;
+  for (int r0 = wave_g * 2; r0 < n_row; r0 += n_waves * 2) {
+    const int r = r0 + hw;
+    const bool row_ok = r < n_row;
+    const int t0 = nt0, t1 = nt1;                                    // (an unpaired last half: t0 = t1 = 0, no token)
+    const int pi_first = npi;
+    {
+      const int rn = r + n_waves * 2;
+      nt0 = nt1 = 0;
+      if (rn < n_row) {
+        nt0 = row_first[rn];
+        nt1 = min(row_first[rn + 1], tok_cap);
+      }
+    }
+    const bf16x8 qv = (row_ok && in_dim) ? *reinterpret_cast<const bf16x8*>(qn_row + (int64_t)r * dim + d0) : z;
+    const float srow = row_ok ? sum_row[r] : 0.f;
+    const int nvrow = (row_ok && n_valid_row) ? n_valid_row[r] : 0, rkrow = (row_ok && rank_row) ? rank_row[r] : 0;
+    const int len = t1 - t0;
+    const int len_max = max(__shfl(len, 0, 64), __shfl(len, 32, 64));
+    for (int off = 0; off < len_max; off += 32) {
+      const int tk = t0 + off + hl;
+      const bool live = tk < t1;
+      int pi = pi_first;
+      if (off != 0) pi = live ? p_idx[tk] : 0;                       // (wave-uniform: rows of more than 32 tokens)
+      const int slot = live ? (slot_of_row ? slot_of_row[pi] : pi) : 0;
+      const int cnt = max(0, min(32, len - off));
+      const int cnt_max = max(__shfl(cnt, 0, 64), __shfl(cnt, 32, 64));
+      float sp = 0.f;
+      for (int i = 0; i < cnt_max; i += FB) {                        // FB target rows requested, then their dot products
+        bf16x8 pv[FB];
+#pragma unroll
+        for (int u = 0; u < FB; ++u) {
+          const int pj = __shfl(pi, hw * 32 + min(i + u, 31), 64);
+          pv[u] = (i + u < cnt && in_dim) ? *reinterpret_cast<const bf16x8*>(pn_rows + (int64_t)pj * dim + d0) : z;
+        }
+#pragma unroll
+        for (int u = 0; u < FB; ++u) {
+          if (i + u >= cnt_max) break;                               // (wave-uniform)
+          float s = 0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) s += (float)qv[e] * (float)pv[u][e];
+          s = half_sum(s);
+          if (hl == i + u) sp = s;
+        }
+      }
+      const int any = live ? fix_any[slot] : 0;
+      float corr = 0.f;
+      int hits = 0, above = 0;
+      uint64_t hm = __ballot(any != 0);
+      while (hm) {                                                   // tokens with suppressed negatives: a few per cent
+        const int i = __builtin_ctzll(hm);
+        hm &= hm - 1;
+        const int any_h = __builtin_amdgcn_readlane(any, i), slot_h = __builtin_amdgcn_readlane(slot, i);
+        const int r_h = __builtin_amdgcn_readlane(r, i & 32);
+        const float sp_h = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sp), i));
+        float q4[4] = {0.f, 0.f, 0.f, 0.f};
+        if (in_dim_w) {
+          const bf16x4 qw = *reinterpret_cast<const bf16x4*>(qn_row + (int64_t)r_h * dim + d0w);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) q4[e] = (float)qw[e];
+        }
+        float corr_h = 0.f;
+        int hits_h = 0, above_h = 0;
+        for_each_hit(fixw, n_tiles, n_rows_pad, slot_h, n_neg, lane, (uint32_t)any_h, [&](int j) {
+          float sj = 0.f;
+          if (in_dim_w) {
+            const bf16x4 nv = *reinterpret_cast<const bf16x4*>(negs + (int64_t)j * dim + d0w);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sj += q4[e] * (float)nv[e];
+          }
+          sj = wave_sum(sj);
+          corr_h += __builtin_amdgcn_exp2f(sj * c1 - c1);
+          hits_h += 1;
+          above_h += sj > sp_h ? 1 : 0;
+        });
+        if (lane == i) {
+          corr = corr_h;
+          hits = hits_h;
+          above = above_h;
+        }
+      }
+      if (live) {                                                    // lane = token: consecutive addresses
+        s_pos[tk] = sp;
+        sum_tok[tk] = fmaxf(srow - corr, 0.f);
+        if (n_valid_row) n_valid_tok[tk] = nvrow - hits;
+        if (rank_row) rank_tok[tk] = max(rkrow - above, 0);
+      }
+    }
+    npi = nt0 + hl < nt1 ? p_idx[nt0 + hl] : 0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // backward, per token (the row-wise kernel of nce.hip reading the row's state): dq_rows, dp_rows, d(logit_scale), lw,
 // and the suppressed pairs taken back out of U (token side) and of d_negs (negative side)
 // ------------------------------------------------------------------------------------------
@@ -365,6 +512,10 @@ __global__ __launch_bounds__(256) void shared_bwd_rows_kernel(
   const float scale = clamp_scale(logit_scale_dev);
   const float c1 = scale * LOG2E;
   float dls = 0.f;
+  // target rows in flight per half.  cfg1 step, kernel trace on one box: 2 rows (121 VGPRs, 4 waves per SIMD) 108 us; 4 rows with
+  // the row's own vectors loaded behind the token loop (116 VGPRs, 4 waves) 84 us; 8 rows (163 VGPRs, 3 waves) 91 us - the
+  // last two with the device-sized grid and the store into zeroed rows, which were not timed apart from it
+  constexpr int RB = 4;
   __shared__ float xpose[4][2][256];
   float* xp = xpose[threadIdx.x >> 6][hw];
   const int d0 = hl * 8, d0w = lane * 4;
@@ -379,26 +530,28 @@ __global__ __launch_bounds__(256) void shared_bwd_rows_kernel(
     for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
   };
+  // the next trip's row bounds are requested a trip ahead
+  int nt0 = 0, nt1 = 0;
+  if (wave_g * 2 + hw < n_row) {
+    nt0 = row_first[wave_g * 2 + hw];
+    nt1 = min(row_first[wave_g * 2 + hw + 1], tok_cap);
+  }
   for (int r0 = wave_g * 2; r0 < n_row; r0 += n_waves * 2) {
     const int r = r0 + hw;
     const bool row_ok = r < n_row;
     const int rr = row_ok ? r : n_row - 1;
-    const int t0 = row_ok ? row_first[rr] : 0, t1 = row_ok ? min(row_first[rr + 1], tok_cap) : 0;
-    float q8[8], u8[8], ap[8], au[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) q8[e] = u8[e] = ap[e] = au[e] = 0.f;
-    if (in_dim) {
-      const bf16x8 qb = *reinterpret_cast<const bf16x8*>(qn_row + (int64_t)rr * dim + d0);
-      const f32x4 ua = *reinterpret_cast<const f32x4*>(u_row + (int64_t)rr * dim + d0);
-      const f32x4 ub = *reinterpret_cast<const f32x4*>(u_row + (int64_t)rr * dim + d0 + 4);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) q8[e] = (float)qb[e];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        u8[e] = ua[e];
-        u8[4 + e] = ub[e];
+    const int t0 = nt0, t1 = nt1;                              // (0, 0 for an unpaired last half)
+    {
+      const int rn = r + n_waves * 2;
+      nt0 = nt1 = 0;
+      if (rn < n_row) {
+        nt0 = row_first[rn];
+        nt1 = min(row_first[rn + 1], tok_cap);
       }
     }
+    float ap[8], au[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ap[e] = au[e] = 0.f;
     float auw[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // hit-path corrections of half 0 / 1's row, 4-col layout
     bool any_hit[2] = {false, false};                                  // (wave-uniform)
     float a_sum = 0.f, lw_m = INFINITY, lw_s = 0.f;
@@ -437,12 +590,12 @@ __global__ __launch_bounds__(256) void shared_bwd_rows_kernel(
       }
       const int cnt = max(0, min(32, len - off));
       const int cnt_max = max(__shfl(cnt, 0, 64), __shfl(cnt, 32, 64));
-      for (int i = 0; i < cnt_max; i += 2) {                   // two target rows in flight per half, added in token order
-        bf16x8 pb[2];
-        float cf[2];
-        bool on[2];
+      for (int i = 0; i < cnt_max; i += RB) {                  // RB target rows in flight per half, added in token order
+        bf16x8 pb[RB];
+        float cf[RB];
+        bool on[RB];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
+        for (int u = 0; u < RB; ++u) {
           on[u] = i + u < cnt;
           const int from = hw * 32 + min(i + u, 31);
           cf[u] = __shfl(coef, from, 64);
@@ -450,7 +603,7 @@ __global__ __launch_bounds__(256) void shared_bwd_rows_kernel(
           if (on[u] && in_dim) pb[u] = *reinterpret_cast<const bf16x8*>(pn + (int64_t)pj * dim + d0);   // the token's target row
         }
 #pragma unroll
-        for (int u = 0; u < 2; ++u)
+        for (int u = 0; u < RB; ++u)
           if (on[u] && in_dim) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) ap[e] += cf[u] * (float)pb[u][e];
@@ -530,6 +683,23 @@ __global__ __launch_bounds__(256) void shared_bwd_rows_kernel(
         }
         __builtin_amdgcn_wave_barrier();
       }
+    // the row's own vectors are needed from here on only (the visits above read the query in their own layout): loaded now,
+    // they do not occupy 16 registers under the target rows in flight
+    float q8[8], u8[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q8[e] = u8[e] = 0.f;
+    if (in_dim) {
+      const bf16x8 qb = *reinterpret_cast<const bf16x8*>(qn_row + (int64_t)rr * dim + d0);
+      const f32x4 ua = *reinterpret_cast<const f32x4*>(u_row + (int64_t)rr * dim + d0);
+      const f32x4 ub = *reinterpret_cast<const f32x4*>(u_row + (int64_t)rr * dim + d0 + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) q8[e] = (float)qb[e];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        u8[e] = ua[e];
+        u8[4 + e] = ub[e];
+      }
+    }
     float dqn[8];
     float dot_q = 0.f, dot_raw = 0.f;
 #pragma unroll
@@ -545,9 +715,15 @@ __global__ __launch_bounds__(256) void shared_bwd_rows_kernel(
     if (exclusive_rows) {
       // no other (group, row) writes this query row (the groups use disjoint heads): a plain 32-byte read-modify-write per lane
       // instead of 256 float atomics per row (15.7 M per step at cfg1 - what this kernel's time went into)
+      // exclusive_rows == 2: the caller also guarantees that the rows hold zeros (a buffer zeroed for this backward, which
+      // this launch alone writes): the read is dropped, and 0 + x is what gets stored, the read-modify-write's value bit for bit
       if (row_ok && in_dim) {
         f32x4* dst = reinterpret_cast<f32x4*>(dq_rows + (int64_t)row_q[rr] * dim + d0);
-        f32x4 v0 = dst[0], v1 = dst[1];
+        f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = {0.f, 0.f, 0.f, 0.f};
+        if (exclusive_rows != 2) {
+          v0 = dst[0];
+          v1 = dst[1];
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           v0[e] += (dqn[e] - q8[e] * dot_q) * iq;
@@ -719,7 +895,49 @@ __global__ __launch_bounds__(256) void row_lw_kernel(const float* __restrict__ l
   lw_row[r] = out;
 }
 
+// Workgroups per group for the row-striding kernels: the device's compute units x 8 workgroups of 4 waves (what a CU holds at
+// <= 64 VGPRs), shared among the groups, and never more than the rows can use (8 rows per workgroup and trip).
+int row_grid_blocks(int row_cap, int n_groups) {
+  static int cus[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (cus[dev] <= 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev] = n;
+  }
+  int blocks = (cus[dev] * 8 + n_groups - 1) / n_groups;
+  const int need = (row_cap + 7) / 8;
+  if (blocks > need) blocks = need;
+  if (blocks > 1024) blocks = 1024;
+  return blocks < 1 ? 1 : blocks;
+}
+
 }  // namespace
+
+extern "C" int mhr_nce_shared_fwd_rows(const void* pn_rows, int64_t n_p_rows, const int32_t* p_idx, const int32_t* row_first,
+                                       const int32_t* n_row_dev, int n_groups, int tok_cap, int row_cap, const void* qn_row,
+                                       const float* sum_row, const int32_t* n_valid_row, const int32_t* rank_row,
+                                       const void* negs, int n_neg, int dim, const float* logit_scale_dev,
+                                       const uint32_t* fix_words, const int32_t* fix_slot_of_row, const int32_t* fix_any,
+                                       float* s_pos, float* sum_tok, int32_t* n_valid_tok, int32_t* rank_tok, void* stream) {
+  MHR_REQUIRE(pn_rows && p_idx && row_first && n_row_dev && qn_row && sum_row && negs && logit_scale_dev && fix_words && fix_any,
+              "nce_shared_fwd_rows: null input pointer");
+  MHR_REQUIRE(s_pos && sum_tok, "nce_shared_fwd_rows: null output pointer");
+  MHR_REQUIRE((n_valid_row != nullptr) == (n_valid_tok != nullptr) && (rank_row != nullptr) == (rank_tok != nullptr),
+              "nce_shared_fwd_rows: row / token log counters go together");
+  MHR_REQUIRE(dim > 0 && dim <= 256 && dim % 8 == 0, "nce_shared_fwd_rows: dim=%d unsupported (multiple of 8, <= 256)", dim);
+  MHR_REQUIRE(tok_cap > 0 && row_cap > 1 && n_neg > 0 && n_p_rows > 0 && n_groups >= 1 && n_groups <= 65535,
+              "nce_shared_fwd_rows: bad sizes");
+  MHR_REQUIRE((uintptr_t)pn_rows % 16 == 0 && (uintptr_t)qn_row % 16 == 0, "nce_shared_fwd_rows: rows must be 16-byte aligned");
+  const int n_rows_pad = (int)((n_p_rows + 255) / 256 * 256);
+  hipLaunchKernelGGL(shared_rows_fwd_kernel, dim3(row_grid_blocks(row_cap, n_groups), 1, n_groups), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16_t*)pn_rows, (int)n_p_rows, p_idx, row_first, n_row_dev, tok_cap, row_cap,
+                     (const bf16_t*)qn_row, sum_row, n_valid_row, rank_row, (const bf16_t*)negs, n_neg, dim, logit_scale_dev,
+                     fix_words, n_rows_pad, fix_slot_of_row, fix_any, s_pos, sum_tok, n_valid_tok, rank_tok);
+  MHR_CHECK_LAUNCH("nce_shared_fwd_rows");
+  return MHR_OK;
+}
 
 extern "C" int mhr_nce_shared_fwd_tokens(const void* pn_rows, int64_t n_p_rows, const int32_t* p_idx,
                                          const int32_t* tok2row, int n_groups, const int32_t* n_tok_dev, int tok_cap,
@@ -791,12 +1009,17 @@ extern "C" int mhr_nce_shared_bwd_rows(const void* qn_row, const float* u_row, c
   const int n_rows_pad = (int)((n_p_rows + 255) / 256 * 256);
   int blocks = (row_cap + 31) / 32;                 // 4 waves x 2 rows x 4 passes (more, smaller workgroups were slower: 0.126 -> 0.15 ms)
   if (blocks > 1024) blocks = 1024;
+  // Sized by the device rather than by the capacity - except with ordered d(logit_scale) partials: their value depends on which
+  // rows a workgroup sums, and the deterministic mode's bits are kept as they were
+  if (!dls_part) blocks = min(blocks, row_grid_blocks(row_cap, n_groups));
+  MHR_REQUIRE(exclusive_rows >= 0 && exclusive_rows <= 2, "nce_shared_bwd_rows: exclusive_rows=%d (0 atomics, 1 read-modify-write, 2 store)",
+              exclusive_rows);
   MHR_REQUIRE(!exclusive_rows || ((uintptr_t)dq_rows % 16 == 0), "nce_shared_bwd_rows: exclusive_rows needs a 16-byte aligned dq_rows");
   hipLaunchKernelGGL(shared_bwd_rows_kernel, dim3(blocks, 1, n_groups), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)qn_row, u_row, q_inv_row, row_q, row_first, n_row_dev, row_cap, (const bf16_t*)pn, dim, tok_cap,
                      logit_scale_dev, lse, w, s_pos, p_idx, dq_rows, d_logit_scale, lw_row, w_bucket, n_buckets,
                      (const bf16_t*)negs, n_neg, fix_words, n_rows_pad, (int)n_p_rows, fix_slot_of_row, fix_any, d_negs,
-                     exclusive_rows ? 1 : 0, (long long*)dn_fix, dls_part);
+                     exclusive_rows, (long long*)dn_fix, dls_part);
   MHR_CHECK_LAUNCH("nce_shared_bwd_rows");
   return MHR_OK;
 }

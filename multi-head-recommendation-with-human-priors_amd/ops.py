@@ -19,15 +19,17 @@ F32, BF16 = lib.F32, lib.BF16
 PROFILE = None
 
 
-def _timed_call(name, *args):
+def _timed_call(name, *args, entry=None):
+    """`entry`: the C entry point to call when it is not `name` (a stage that changed its kernel keeps its name in the profile)."""
+    entry = entry or name
     if PROFILE is not None and name in PROFILE:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        lib.call(name, *args)
+        lib.call(entry, *args)
         e1.record()
         PROFILE[name].append((e0, e1))
     else:
-        lib.call(name, *args)
+        lib.call(entry, *args)
 
 
 def profile_summary(with_max=False):
@@ -1143,12 +1145,14 @@ def _nce_fwd_shared(c, q_rows, p_rows, logit_scale, want_logs, log_group, p_row_
                 q_inv_row.data_ptr(), p_inv_row.data_ptr(), s_pos_row.data_ptr(), int(log_group), u_row.data_ptr(), n_p_rows,
                 *fix_args, st)
     # (3) per token: s+, sums and counters with the token's own suppressed negatives taken out, against prep.pn_rows (one
-    #     l2norm pass over p_rows: the normalised target is a property of the TARGET ROW)
+    #     l2norm pass over p_rows: the normalised target is a property of the TARGET ROW).  A half-wave per query row
+    #     (mhr_nce_shared_fwd_rows: the per-token entry's values bit for bit), timed under the stage's name
     ssum = torch.empty(G, cap, dtype=torch.float32, device=dev)
-    _timed_call("mhr_nce_shared_fwd_tokens", prep.pn_rows.data_ptr(), n_p_rows, p_idx.data_ptr(), prep.tok2row.data_ptr(), G,
-                n_tok_dev.data_ptr(), cap, row_cap, qn_row.data_ptr(), prep.sum_row.data_ptr(), _ptr(prep.nv_row), _ptr(prep.rk_row),
-                negs.data_ptr(), n_neg, D, logit_scale.data_ptr(), prep.fix_words.data_ptr(), _ptr(prep.slot_of_row),
-                prep.fix_any.data_ptr(), s_pos.data_ptr(), ssum.data_ptr(), _ptr(prep.n_valid), _ptr(prep.rank), st)
+    _timed_call("mhr_nce_shared_fwd_tokens", prep.pn_rows.data_ptr(), n_p_rows, p_idx.data_ptr(), prep.row_first.data_ptr(),
+                prep.n_row.data_ptr(), G, cap, row_cap, qn_row.data_ptr(), prep.sum_row.data_ptr(), _ptr(prep.nv_row),
+                _ptr(prep.rk_row), negs.data_ptr(), n_neg, D, logit_scale.data_ptr(), prep.fix_words.data_ptr(),
+                _ptr(prep.slot_of_row), prep.fix_any.data_ptr(), s_pos.data_ptr(), ssum.data_ptr(), _ptr(prep.n_valid),
+                _ptr(prep.rank), st, entry="mhr_nce_shared_fwd_rows")
     own = dict(qn=qn_row, u=u_row, q_inv=q_inv_row, supp=supp_row, pn=prep.pn_rows, p_inv=prep.p_inv, tok2row=prep.tok2row,
                row_first=prep.row_first, row_q=prep.row_q, n_row_dev=prep.n_row, row_cap=row_cap, fix_words=prep.fix_words,
                fix_slot=prep.slot_of_row, fix_any=prep.fix_any, n_p_rows=n_p_rows, window=window, bwd_bufs=prep.bwd)
@@ -1238,14 +1242,16 @@ def nce_fwd(q_rows, q_idx, p_rows, p_idx, negs, n_tok_dev, tok_cap, logit_scale,
 
 
 def nce_bwd(sv, w, logit_scale, q_idx, p_idx, dq_rows, dp_rows, d_negs=None, d_logit_scale=None, want_negs=True, lw_row=None,
-            exclusive_q_rows=False):
+            exclusive_q_rows=False, dq_rows_zero=False):
     """w [G, tok_cap] f32 = dLoss/dloss[g, t] - or [G, n_buckets] when the forward was given bucket_idx (every token
     of a bucket then has the same weight).  Accumulates into dq_rows [Rq, D] / dp_rows [Rp, D] (f32, the
     forward's shared row spaces); returns (d_negs [G, n_neg, D] f32, d_logit_scale [1]).  q_idx / p_idx are the
     forward's index lists (the padded copies saved by nce_fwd are what the kernels read).  want_negs=False skips the
     negative-side product (frozen negatives, e.g. the HLLM twin's cached item tower) and returns d_negs = None.
     exclusive_q_rows: no two (group, query-row) pairs of the forward name the same row of dq_rows (the groups read disjoint
-    decoding heads): the row-wise backward then adds with plain read-modify-writes instead of float atomics."""
+    decoding heads): the row-wise backward then adds with plain read-modify-writes instead of float atomics.
+    dq_rows_zero (with exclusive_q_rows): dq_rows holds zeros and nothing but this call writes it before it is read: the row-wise
+    backward stores the row gradients without reading the zeros back (same bits)."""
     dev = sv.negs.device
     D, cap, G = sv.dim, sv.cap, sv.groups
     if w.dim() == 1:
@@ -1267,14 +1273,16 @@ def nce_bwd(sv, w, logit_scale, q_idx, p_idx, dq_rows, dp_rows, d_negs=None, d_l
         w_tok = torch.gather(w, 1, sv.bucket_idx.long().clamp(0, sv.n_buckets - 1)) if bucketed else w
         wide.nce_bwd_wide(sv, w_tok, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale)
     elif sv.shared:
-        _nce_bwd_shared(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale, want_negs, lw_row, exclusive_q_rows)
+        _nce_bwd_shared(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale, want_negs, lw_row,
+                        (2 if dq_rows_zero else 1) if exclusive_q_rows else 0)
     else:
         _nce_bwd_tokens(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale, want_negs)
     return d_negs, d_logit_scale
 
 
-def _nce_bwd_shared(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale, want_negs, lw_row, exclusive_q_rows):
-    """Row-wise / target-wise kernels for window-structured lists, else per-token atomics; then the negative-side product over the rows."""
+def _nce_bwd_shared(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_logit_scale, want_negs, lw_row, exclusive_rows):
+    """Row-wise / target-wise kernels for window-structured lists, else per-token atomics; then the negative-side product over the rows.
+    exclusive_rows: mhr_nce_shared_bwd_rows' mode (0 float atomics, 1 read-modify-write, 2 store into zeroed rows)."""
     dev, D, cap, G, st = sv.negs.device, sv.dim, sv.cap, sv.groups, _stream()
     dn_ptr = d_negs.data_ptr() if want_negs else 0
     if lw_row is None:                   # (+inf: a row the kernels do not visit contributes nothing to the negative-side product)
@@ -1291,7 +1299,7 @@ def _nce_bwd_shared(sv, w, wb_ptr, nb, logit_scale, dq_rows, dp_rows, d_negs, d_
                     logit_scale.data_ptr(), sv.lse.data_ptr(), w.data_ptr(), sv.s_pos.data_ptr(), sv.p_idx.data_ptr(),
                     dq_rows.data_ptr(), d_logit_scale.data_ptr(), lw_row.data_ptr(), wb_ptr, nb, sv.negs.data_ptr(), sv.n_neg,
                     sv.fix_words.data_ptr(), sv.n_p_rows, _ptr(sv.fix_slot), sv.fix_any.data_ptr(), dn_ptr,
-                    1 if exclusive_q_rows else 0, _ptr(dn_fix), _ptr(dls_part), st)
+                    int(exclusive_rows), _ptr(dn_fix), _ptr(dls_part), st)
         if dls_part is not None:         # the workgroups' partials of d(logit_scale), folded in index order
             lib.call("mhr_det_sum_into", dls_part.data_ptr(), dls_part.numel(), logit_scale.data_ptr(), 1, d_logit_scale.data_ptr(), st)
         _timed_call("mhr_nce_shared_bwd_targets", sv.qn.data_ptr(), sv.row_cap, sv.tok2row.data_ptr(), tos.data_ptr(),
